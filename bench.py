@@ -11,6 +11,12 @@ decodes its own batch (weak scaling) with no data-path collective; ranks only ba
 around the timed region and all_reduce(MAX) the elapsed time.
 
 Output: one JSON line on rank 0 (see DESIGN.md §Measurement for every field).
+
+A plain run does what the headline figure needs and no more: set-up, warm-up, the K timed
+steps, the result line (and --dump-outputs DIR: the last timed step's outputs as .npy files).
+--full adds everything else the benchmark measures or checks: the CPU baseline and oracle
+parity, the other BASELINE configs nested under "configs", the training step timed with its
+collective issued, and the full record file.
 """
 import argparse
 import json
@@ -94,8 +100,17 @@ def parse():
     p.add_argument('--iters', type=int, default=None)
     p.add_argument('--dtype', default='f32', choices=['f32', 'f64', 'bf16'],
                    help='bf16 (decode, classical models): bf16 x/out in HBM, fp32 arithmetic')
-    p.add_argument('--cpu-seconds', type=float, default=12.0,
-                   help='bounded CPU-baseline sample (0 disables)')
+    p.add_argument('--full', action='store_true',
+                   help='beside the headline figure also measure and check everything else: the '
+                        'CPU baseline and oracle parity (--cpu-seconds), the other BASELINE configs '
+                        '(--configs), the collective-inclusive training step, and the full record '
+                        'file.  A plain run sets up, warms up, times the K steps and prints its line')
+    p.add_argument('--dump-outputs', default=None, metavar='DIR',
+                   help='after the timed steps, write what the last timed step computed (the '
+                        'arrays a caller of the timed path receives) as DIR/<name>.npy, float32 or '
+                        'float64, at most 64 MB in all (a fixed seeded sample of larger outputs)')
+    p.add_argument('--cpu-seconds', type=float, default=None,
+                   help='--full: bounded CPU-baseline sample (default 12; 0 disables)')
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--weights', default='auto', choices=['auto', 'random'],
                    help='auto: the shipped trained weights of this model/code when present '
@@ -114,8 +129,8 @@ def parse():
                    help='train mode: torch autograd/optimizer Trainer around the fused kernels '
                         'instead of FusedV24Trainer')
     p.add_argument('--configs', default='auto', choices=['auto', 'on', 'off'],
-                   help='decode mode: also time BASELINE configs 3-5 in the same process and nest '
-                        'them under "configs" (auto: for the default headline workload)')
+                   help='--full, decode mode: also time BASELINE configs 3-5 in the same process and '
+                        'nest them under "configs" (auto: for the default headline workload)')
     p.add_argument('--priors', default='auto', choices=['auto', 'off'],
                    help='fp64 decoder_v2_4 decodes: tabulate the variable-side MLP per channel '
                         'prior of the batch (gnnd_prepare_weights_priors; auto) or not (off)')
@@ -123,7 +138,17 @@ def parse():
                    help='train = config 5: decoder_v2_4 (or --model qgnni/nbp/v10) training '
                         'step (DP, RCCL all-reduce); sample = the on-device input synthesis '
                         'kernel alone (gnnd_sample_*, HBM-write bound)')
-    return p.parse_args()
+    a = p.parse_args()
+    if a.full:
+        if a.cpu_seconds is None:
+            a.cpu_seconds = 12.0
+    else:
+        # a plain run measures the headline figure alone: no CPU legs, no other configs, no
+        # second training timing with the collective issued
+        if a.cpu_seconds or a.configs == 'on':
+            p.error('--cpu-seconds > 0 and --configs on need --full')
+        a.cpu_seconds, a.configs, a.collective = 0.0, 'off', False
+    return a
 
 
 # provenance of the shipped weights (gnn-decode_amd/gnndecode/weights/README.md)
@@ -133,6 +158,29 @@ WEIGHT_SOURCES = {
     'qgnni_toric_5': 'trained by tools/train_qgnni_toric.py',
     'v24_toric_5': 'reference checkpoint quantum/new_model/decoder_parameters_epoch67.pkl, converted',
 }
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write each tensor of `arrays` (name -> tensor, first dimension = codewords
+    or samples) as <path>/<name>.npy in float32 (float64 tensors stay float64).  The byte budget
+    is shared evenly; a larger tensor is cut to a fixed sample of its rows (torch.randperm,
+    seed 0, ascending), the same rows in every run with the same arguments."""
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dim() == 0:
+            t = t.reshape(1)
+        wide = torch.float64 if t.dtype == torch.float64 else torch.float32
+        row_bytes = max(1, t[0].numel()) * (8 if wide == torch.float64 else 4)
+        keep = max(1, budget // row_bytes)
+        if t.shape[0] > keep:
+            perm = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))
+            t = t.index_select(0, perm[:keep].sort().values.to(t.device))
+        np.save(os.path.join(path, name + '.npy'), t.to(wide).cpu().numpy())
 
 
 def load_pmc(tag):
@@ -414,6 +462,8 @@ def sample_main(a, world, rank, dev):
     if dist.is_initialized():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {'x': x.view(a.batch, -1), 'y': y.view(a.batch, -1)})
     if rank == 0:
         V, C = H.shape
         esz = 8 if dtype == torch.float64 else 4
@@ -588,6 +638,11 @@ def train_run(a, world, rank, dev, cpu='full'):
                                gd.train.FusedWbpTrainer, gd.train.FusedGnnTrainer))
     elapsed, issue_s, loss, gpu_s = time_train_steps(tr, data, y, a.steps, fused_tr)
     timed_ns = list(TIMED_NS)
+    if rank == 0 and getattr(a, 'dump_outputs', None):
+        # what a caller of the K steps holds afterwards: the last step's loss, the parameters
+        dump_outputs(a.dump_outputs, {
+            'loss': torch.as_tensor(loss).detach().reshape(-1),
+            'params': torch.cat([p.detach().reshape(-1) for p in model.parameters()])})
     # the same step with its RCCL all_reduce(SUM) of the flat gradient + loss actually issued:
     # N > 1 runs already contain it; a 1-GPU run times it on a 1-rank RCCL group
     # (force_collective), from the same starting weights on the same batch
@@ -845,6 +900,11 @@ def decode_run(a, world, rank, dev, cpu='full'):
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed_decode_only, elapsed = elapsed, float(t.item())
 
+    if rank == 0 and getattr(a, 'dump_outputs', None):
+        # what the last timed step left in `out` (one row of the dump per codeword)
+        dump_outputs(a.dump_outputs, {'out': out.view(a.batch, -1) if out.numel() % a.batch == 0
+                                      else out})
+
     # hard-decision error rate of this batch (outside the timed region)
     with torch.no_grad():
         # one launch: bit errors, frame errors, residual-syndrome / logical failures (toric)
@@ -1022,6 +1082,7 @@ def sub_config_results(a, world, rank, dev):
         for k, v in ov.items():
             setattr(sa, k, v)
         sa.iters, sa.weights, sa.seed = None, 'auto', a.seed
+        sa.dump_outputs = None                   # the dump is the headline run's alone
         sa.cpu_seconds = min(a.cpu_seconds, 2.0)
         t0 = time.perf_counter()
         if mode == 'train':
@@ -1254,7 +1315,9 @@ def main():
                 res['scaling_efficiency_global128'] = strong_scaling(sub)
     if rank == 0 and res is not None:
         res['dist'] = ranks
-        print(driver_line(res, write_full_record(res)), flush=True)
+        # the full record file belongs to --full (or to a caller that names one)
+        keep = a.full or 'GNND_BENCH_FULL' in os.environ
+        print(driver_line(res, write_full_record(res) if keep else None), flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()
 

@@ -77,6 +77,53 @@ def test_launch_mode_option(monkeypatch):
     assert bench.parse().launch == 'graph'
 
 
+def test_plain_run_measures_the_headline_alone(monkeypatch):
+    """Without --full: no CPU legs, no nested configs, no second (collective) training timing;
+    asking for them without --full is an error.  --full keeps today's defaults."""
+    import sys
+    import pytest
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.cpu_seconds == 0 and a.configs == 'off' and a.collective is False
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--cpu-seconds', '0', '--configs', 'off'])
+    assert bench.parse().cpu_seconds == 0
+    for bad in (['--cpu-seconds', '2'], ['--configs', 'on']):
+        monkeypatch.setattr(sys, 'argv', ['bench.py'] + bad)
+        with pytest.raises(SystemExit):
+            bench.parse()
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full'])
+    a = bench.parse()
+    assert a.full and a.cpu_seconds == 12.0 and a.configs == 'auto' and not hasattr(a, 'collective')
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--cpu-seconds', '0', '--dump-outputs', 'd'])
+    a = bench.parse()
+    assert a.cpu_seconds == 0 and a.dump_outputs == 'd'
+
+
+def test_dump_outputs_types_budget_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 (float64 stays float64) .npy per name; an output over the byte
+    budget is cut to the same ascending sample of rows in every run."""
+    g = torch.Generator().manual_seed(1)
+    small = torch.randn(5, 3, generator=g).bfloat16()
+    wide = torch.randn(4, 2, generator=g, dtype=torch.float64)
+    big = torch.randn(1000, 8, generator=g)
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 3 * 100 * 8 * 4)     # 100 rows of `big` each
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), {'small': small, 'wide': wide, 'big': big,
+                                               'scalar': torch.tensor(2.5)})
+    ld = lambda d, n: np.load(tmp_path / d / (n + '.npy'))
+    assert ld('a', 'small').dtype == np.float32 and (ld('a', 'small') == small.float().numpy()).all()
+    assert ld('a', 'wide').dtype == np.float64 and (ld('a', 'wide') == wide.numpy()).all()
+    assert ld('a', 'scalar').tolist() == [2.5]
+    got = ld('a', 'big')
+    assert got.dtype == np.float32 and got.shape == (75, 8)             # budget / 4 names
+    assert (got == ld('b', 'big')).all()
+    rows = [int(np.flatnonzero((big.numpy() == r).all(1))[0]) for r in got]
+    assert rows == sorted(set(rows))
+    total = sum(ld('a', n).nbytes for n in ('small', 'wide', 'big', 'scalar'))
+    assert total <= bench.DUMP_LIMIT_BYTES
+
+
 def _full_size_record():
     """The round-4 default run's full record (20 KB, every nested field), widened to the round-5
     config list and an 8-rank job: the largest line the driver can see."""

@@ -22,7 +22,7 @@ if [ $# -ge 2 ]; then mapfile -t RUNS < "$2"; else RUNS=(
 for args in "${RUNS[@]}"; do
   [ -z "$args" ] && continue
   echo "=== $args ($(date +%T))"
-  timeout -k 10 300 python bench.py $args > "$OUT.tmp" 2>&1
+  timeout -k 10 300 python bench.py --full $args > "$OUT.tmp" 2>&1
   rc=$?
   if [ $rc -ne 0 ]; then echo "FAIL rc=$rc: $args"; tail -5 "$OUT.tmp"; exit $rc; fi
   grep '^{' "$OUT.tmp" | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); d['args']='$args'; print(json.dumps(d))" >> "$OUT"

@@ -8,7 +8,7 @@ OUT="$1"; mkdir -p "$OUT"
 run() {  # name timeout args...
   local name=$1 to=$2; shift 2
   echo "=== $name: $*"
-  timeout -k 10 "$to" python bench.py "$@" > "$OUT/$name.log" 2>&1
+  timeout -k 10 "$to" python bench.py --full "$@" > "$OUT/$name.log" 2>&1
   local rc=$?
   grep '^{' "$OUT/$name.log" >> "$OUT/configs.jsonl"
   echo "--- $name exit $rc"; tail -2 "$OUT/$name.log" | cut -c1-400

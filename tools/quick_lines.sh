@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 i=0
 for a in "$@"; do
   i=$((i + 1))
-  timeout -k 10 300 python bench.py $a --cpu-seconds ${CPU_SECONDS:-2} --configs off > "$OUT/line_$i.txt" 2>&1 || { echo "FAIL: $a"; tail -5 "$OUT/line_$i.txt"; exit 3; }
+  timeout -k 10 300 python bench.py --full $a --cpu-seconds ${CPU_SECONDS:-2} --configs off > "$OUT/line_$i.txt" 2>&1 || { echo "FAIL: $a"; tail -5 "$OUT/line_$i.txt"; exit 3; }
   grep '^{' "$OUT/line_$i.txt" | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read()); r = d.get('roofline') or {}; c = d.get('config') or {}; cb = d.get('cpu_baseline') or {}

@@ -17,7 +17,7 @@ line() {  # tag args...
   grep '^{' "$OUT/$tag.log" | tail -1 > "$OUT/$tag.json"
   python -c "import json; d=json.load(open('$OUT/$tag.json')); print('$tag', '%.4g' % d['value'], round(d['ms_per_step'], 3), d['roofline'] and d['roofline'].get('frac'), (d.get('cpu_baseline') or {}).get('hard_decision_mismatches'))"
 }
-line c3_v24_toric5_f64 --model v24 --code toric_5 --dtype f64 --steps 10 --warmup 2 --cpu-seconds 20
+line c3_v24_toric5_f64 --full --model v24 --code toric_5 --dtype f64 --steps 10 --warmup 2 --cpu-seconds 20
 line v24_toric7_f64 --model v24 --code toric_7 --dtype f64 --batch 16384 --steps 10 --warmup 2 --cpu-seconds 0
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
     python bench.py --model v24 --code toric_5 --dtype f64 --steps 10 --warmup 2 --cpu-seconds 0 > "$OUT/prof.log" 2>&1 || fail prof $?
