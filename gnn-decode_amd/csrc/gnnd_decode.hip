@@ -119,14 +119,38 @@ extern "C" int gnnd_prepare_weights_priors(int model, int dtype, const void* d_w
     if (rc != GNND_OK || n_priors == 0) return rc;
     // (after gnnd_prepare_weights on the same stream: its check-MLP build zeroes the header,
     // the table build then writes the count)
-    VtPriors pr{};
-    for (int i = 0; i < n_priors; ++i) pr.x[i] = h_priors[i];
+    VtHostList src{};
+    for (int i = 0; i < n_priors; ++i) src.pr.x[i] = h_priors[i];
+    src.n = n_priors;
     vtab_build_kernel<0><<<dim3(vt_cells(kVtInvG), n_priors), 128, 0, (hipStream_t)stream>>>(
-        (const double*)d_w, (double*)d_prepared, pr, n_priors, 0);
+        (const double*)d_w, (double*)d_prepared, src);
     GNND_LAUNCH_CHECK();
     // the readout MLP's table after them (same form, no prior, finer cells)
     vtab_build_kernel<1><<<dim3(vt_cells(kVtInvR), 1), 128, 0, (hipStream_t)stream>>>(
-        (const double*)d_w, (double*)d_prepared, pr, n_priors, n_priors);
+        (const double*)d_w, (double*)d_prepared, src);
+    GNND_LAUNCH_CHECK();
+    return GNND_OK;
+}
+
+// the same build from a device-resident list (gnnd_v24_scan_priors): the count is not known to
+// the host, so the launch covers kVtMaxPriors rows and the buffer must hold them all
+extern "C" int gnnd_prepare_weights_priors_dev(int model, int dtype, const void* d_w, void* d_prepared,
+                                               int64_t prepared_capacity, const double* d_priors,
+                                               const int32_t* d_status, void* stream) {
+    if (weights_count(model) == -1 || (dtype != GNND_F32 && dtype != GNND_F64)) return GNND_ERR_INVALID_ARG;
+    if (model != GNND_V24 || dtype != GNND_F64) return GNND_ERR_UNSUPPORTED;
+    if (!d_w || !d_prepared || d_w == d_prepared || !d_priors || !d_status) return GNND_ERR_INVALID_ARG;
+    if (prepared_capacity < kV24PriorOff + (int64_t)kVtMaxPriors * kVtStride + kVtStrideR)
+        return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_prepare_weights(model, dtype, d_w, d_prepared, stream);
+    if (rc != GNND_OK) return rc;
+    // (count 0: both kernels exit at once, the header keeps gnnd_prepare_weights' zero)
+    const VtDevList src{d_priors, d_status};
+    vtab_build_kernel<0><<<dim3(vt_cells(kVtInvG), kVtMaxPriors), 128, 0, (hipStream_t)stream>>>(
+        (const double*)d_w, (double*)d_prepared, src);
+    GNND_LAUNCH_CHECK();
+    vtab_build_kernel<1><<<dim3(vt_cells(kVtInvR), 1), 128, 0, (hipStream_t)stream>>>(
+        (const double*)d_w, (double*)d_prepared, src);
     GNND_LAUNCH_CHECK();
     return GNND_OK;
 }

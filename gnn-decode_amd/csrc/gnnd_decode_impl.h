@@ -649,16 +649,38 @@ constexpr int kVtMaxPriors = 64;
 struct VtPriors {
     double x[kVtMaxPriors];
 };
-// block (j, t): cell j of table t0 + t, one unit per thread; w = the plain packed fp64 weights
-// (may alias prep).  SEL 0: ggc1 with prior pr.x[t]; SEL 1: the readout MLP (prep[kV24PriorHdr + 1]
-// = 1 marks it)
-template <int SEL>
-__global__ void __launch_bounds__(128) vtab_build_kernel(const double* w, double* prep, VtPriors pr, int n,
-                                                         int t0) {
+// Where a table build takes its priors and their count from.  VtHostList: the caller's host
+// list, passed by value with the launch (gnnd_prepare_weights_priors).  VtDevList: a device-
+// resident list and count (gnnd_v24_scan_priors' d_priors / d_status), read by the kernel -- the
+// launch then covers kVtMaxPriors block rows and the rows at and past the count exit.
+struct VtHostList {
+    VtPriors pr;
+    int n;
+    __device__ __forceinline__ int count() const { return n; }
+    __device__ __forceinline__ double prior(int t) const { return pr.x[t]; }
+};
+struct VtDevList {
+    const double* x;          // [kVtMaxPriors]
+    const int32_t* status;    // [0] = count (0: build nothing)
+    __device__ __forceinline__ int count() const {
+        const int n = status[0];
+        return n < 0 ? 0 : (n > kVtMaxPriors ? kVtMaxPriors : n);
+    }
+    __device__ __forceinline__ double prior(int t) const { return x[t]; }
+};
+// block (j, t): cell j of table t, one unit per thread; w = the plain packed fp64 weights
+// (may alias prep).  SEL 0: ggc1 with prior src.prior(t), t < src.count(); SEL 1: the readout
+// MLP's table in slot src.count() (prep[kV24PriorHdr + 1] = 1 marks it)
+template <int SEL, typename SRC>
+__global__ void __launch_bounds__(128) vtab_build_kernel(const double* w, double* prep, SRC src) {
     constexpr int INV = SEL == 0 ? kVtInvG : kVtInvR;
+    const int n = src.count();
+    // (uniform; a host list launches exactly n rows, n > 0)
+    if (n == 0 || (SEL == 0 && (int)blockIdx.y >= n)) return;
+    const int t0 = SEL == 0 ? 0 : n;
     const double* wm = w + (SEL == 0 ? kV24Ggc1 : kV24Mlp);
     const int k = threadIdx.x, j = blockIdx.x;
-    const double x = SEL == 0 ? pr.x[blockIdx.y] : 0.0;
+    const double x = SEL == 0 ? src.prior(blockIdx.y) : 0.0;
     const double W1a = wm[k], W1b = SEL == 0 ? wm[128 + k] : 0.0, b1 = wm[(SEL == 0 ? 256 : 128) + k];
     const double W2 = wm[(SEL == 0 ? 384 : 256) + k], b2 = wm[SEL == 0 ? 512 : 384];
     // the decoder's pre-activation: ggc1 fma(u, W1a, fma(x, W1b, b1)), readout fma(m, W1, b1)

@@ -288,6 +288,8 @@ class _Decoder(torch.nn.Module):
         self._graphs = {}
         self._wcache = None
         self._priors = ()
+        self._auto_flat = None     # 'auto' priors: (key, packed fp64 weights on the device)
+        self._auto_bufs = {}       # ... and per device (prepared buffer, scan scratch)
 
     # ---- graph / weights on the device ------------------------------------------------
     def graph(self, device):
@@ -310,16 +312,47 @@ class _Decoder(torch.nn.Module):
         which device-side updates do not bump: a replayed HIP graph's optimizer step and the
         fused trainer's gnnd_adam_step.  The trainers call this after every step."""
         self._wcache = None
+        self._auto_flat = None
 
     def set_channel_priors(self, priors):
         """decoder_v2_4, fp64: the channel-prior LLRs x_v the inputs carry (one per codeword in
         the reference's gen_syn data; e.g. ops.channel_priors(graph, x)).  The fused decoder then
         reads the variable-side MLP from a table per prior (gnnd_prepare_weights_priors); inputs
-        with other priors still decode exactly (the 128 units).  () to clear."""
+        with other priors still decode exactly (the 128 units).  () to clear.
+        'auto': every fp64 eval forward on the fused path finds its batch's priors on the device
+        and rebuilds the tables from them (ops.prepare_weights_auto: no host round trip, so it
+        works under stream capture and when the p list changes from batch to batch; up to 64
+        distinct priors, more decode through the units).  Other dtypes, training and traced
+        code decode without tables, as with ()."""
         if priors and self.kind != 'v24':
             raise ValueError('channel-prior tables: decoder_v2_4 only')
-        self._priors = tuple(float(v) for v in priors)
+        if isinstance(priors, str):
+            if priors != 'auto':
+                raise ValueError(f"channel priors: a list of LLRs, () or 'auto', got {priors!r}")
+            self._priors = 'auto'
+        else:
+            self._priors = tuple(float(v) for v in priors)
         self._wcache = None
+        self._auto_flat = None
+
+    def _auto_prepared(self, g, x):
+        """'auto' channel priors: the prepared weights with the tables of this batch's priors,
+        rebuilt on every call (whether the priors changed cannot be known without a host read)
+        into buffers kept per device."""
+        dev = str(x.device)
+        key = (dev, tuple(p._version for p in self.parameters()),
+               tuple(p.data_ptr() for p in self.parameters()))
+        if self._auto_flat is None or self._auto_flat[0] != key:
+            flat = self.packed_weights().detach().to(device=x.device, dtype=torch.float64)
+            self._auto_flat = (key, flat.contiguous())
+        bufs = self._auto_bufs.get(dev)
+        if bufs is None:
+            bufs = (torch.empty(ops.prepared_count('v24', torch.float64, priors=ops.MAX_PRIORS),
+                                dtype=torch.float64, device=x.device),
+                    (torch.empty(ops.MAX_PRIORS, dtype=torch.float64, device=x.device),
+                     torch.empty(2, dtype=torch.int32, device=x.device)))
+            self._auto_bufs[dev] = bufs
+        return ops.prepare_weights_auto(g, self._auto_flat[1], x, out=bufs[0], scratch=bufs[1])
 
     def prepared_weights(self, dtype, device):
         key = (dtype, str(device), tuple(p._version for p in self.parameters()),
@@ -329,7 +362,7 @@ class _Decoder(torch.nn.Module):
         flat = self.packed_weights()
         if flat is None:
             return None
-        pri = self._priors if dtype == torch.float64 else None
+        pri = self._priors if dtype == torch.float64 and self._priors != 'auto' else None
         prep = ops.prepare_weights(self.kind, flat.detach().to(device=device, dtype=dtype), priors=pri)
         self._wcache = (key, prep)
         return prep
@@ -354,6 +387,9 @@ class _Decoder(torch.nn.Module):
             g = self.graph(x.device)
             # bf16 inputs (classical models): bf16 storage, fp32 weights and arithmetic
             wdt = torch.float32 if x.dtype == torch.bfloat16 else x.dtype
+            if (self._priors == 'auto' and x.dtype == torch.float64
+                    and not torch.compiler.is_compiling()):
+                return ops.decode(g, self.kind, x, self.Nc, self._auto_prepared(g, x))
             return ops.decode(g, self.kind, x, self.Nc, self.prepared_weights(wdt, x.device))
         if not x.is_cuda:
             raise RuntimeError('gnndecode runs on the GPU only (HIP/gfx950); move data to cuda')

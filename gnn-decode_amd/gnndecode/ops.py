@@ -216,6 +216,63 @@ def channel_priors(graph, x, limit=64):
     return u
 
 
+MAX_PRIORS = 64      # channel-prior tables one prepared buffer holds (kVtMaxPriors)
+
+
+def scan_channel_priors(graph, x, out=None):
+    """channel_priors on the device (gnnd_v24_scan_priors): the distinct first variable inputs
+    of the codewords of x [B*N] (fp64) -- the element the decoder keys a codeword's table on --
+    ascending, as (priors fp64 [64], status int32 [2]) device tensors: priors[:count] the
+    values, zeros after them, status = [count, 0]; more than 64 distinct values: zeros and
+    status = [0, 1].  NaN inputs are skipped.  No host copy and no synchronisation; `out` = an
+    earlier result's pair to write into."""
+    _require_gpu(x)
+    if x.dtype != torch.float64:
+        raise TypeError(f'channel-prior tables are fp64 only, got {x.dtype}')
+    x = x.contiguous()
+    if x.numel() % graph.N:
+        raise ValueError(f'x has {x.numel()} rows, not a multiple of N={graph.N}')
+    if out is None:
+        out = (torch.empty(MAX_PRIORS, dtype=torch.float64, device=x.device),
+               torch.empty(2, dtype=torch.int32, device=x.device))
+    priors, status = out
+    if (priors.dtype != torch.float64 or priors.numel() != MAX_PRIORS or not priors.is_contiguous()
+            or status.dtype != torch.int32 or status.numel() != 2 or not status.is_contiguous()):
+        raise ValueError('out must be (contiguous fp64 [64], contiguous int32 [2])')
+    _require_gpu(priors, status)
+    _lib.call('gnnd_v24_scan_priors', graph.handle, dtype_code(x.dtype), _ptr(x),
+              x.numel() // graph.N, _ptr(priors), _ptr(status), current_stream(x.device))
+    return priors, status
+
+
+def prepare_weights_auto(graph, flat, x, out=None, scratch=None):
+    """prepare_weights('v24', flat, priors=channel_priors(graph, x)) with no host round trip:
+    the batch's priors are found on the device (scan_channel_priors) and the tables built from
+    that device list (gnnd_prepare_weights_priors_dev), all on the current stream.  The count is
+    not known to the host, so the result has prepared_count('v24', float64, priors=64) elements
+    (the tables of the priors found, then the readout table, the rest unused); with more than 64
+    distinct priors it carries no tables.  `out` (that many fp64 elements) and `scratch` (a
+    scan_channel_priors pair) are reused when given.  Returns the prepared tensor."""
+    _require_gpu(flat, x)
+    flat = flat.contiguous()
+    if flat.dtype != torch.float64:
+        raise TypeError(f'channel-prior tables are fp64 only, got {flat.dtype} weights')
+    n = weights_count('v24')
+    if flat.numel() != n:
+        raise ValueError(f'v24: expected {n} packed weights, got {flat.numel()}')
+    cap = prepared_count('v24', torch.float64, priors=MAX_PRIORS)
+    if out is None:
+        out = torch.empty(cap, dtype=torch.float64, device=flat.device)
+    elif out.dtype != torch.float64 or out.numel() < cap or not out.is_contiguous():
+        raise ValueError(f'out must be a contiguous fp64 tensor of at least {cap} elements')
+    _require_gpu(out)
+    priors, status = scan_channel_priors(graph, x, out=scratch)
+    _lib.call('gnnd_prepare_weights_priors_dev', _lib.VARIANT['v24'], dtype_code(flat.dtype),
+              _ptr(flat), _ptr(out), out.numel(), _ptr(priors), _ptr(status),
+              current_stream(flat.device))
+    return out
+
+
 def v24_var_mlp_table(prepared_weights, u, xv=None):
     """gnnd_v24_var_mlp_table: decoder_v2_4's variable-side MLP through the channel-prior tables
     at fp64 points (u, x_v) -> (y, hit) with y = tanh(ggc1.mlp(u, x_v) / 2), the check step's

@@ -196,13 +196,13 @@ int gnnd_weights_count(int model, int64_t* h_count);
 int gnnd_decode_weights_count(const gnnd_graph* g, int model, int32_t iters, int64_t* h_count);
 int gnnd_prepare_weights(int model, int dtype, const void* d_w, void* d_prepared,
                          void* stream);
-/* Elements of gnnd_prepare_weights' output: gnnd_weights_count, except V24 (7 264): the 1 283
- * weights (fp32: base-2 rescaled), then the check-MLP table (gnnd_v24_check_mlp_table) the
- * decoder and training forward read, then an 12-element channel-prior header (0 tables; see
- * gnnd_prepare_weights_priors), and fp32 CGNNI / QGNNI (328): the plain 62, then their message
- * MLP as a piecewise-linear table (<= 32 cells of <= 2 knots) the register-resident decoder
- * reads.  gnnd_decode needs this prepared buffer, not the plain weights (so does
- * gnnd_train_fwd for V24).                                                                  */
+/* Elements of gnnd_prepare_weights' output: gnnd_weights_count, except V24 (7 264, fp32 and
+ * fp64): the 1 283 weights (fp32: base-2 rescaled), then the check-MLP table
+ * (gnnd_v24_check_mlp_table) the decoder and training forward read, then a 12-element
+ * channel-prior header (0 tables; see gnnd_prepare_weights_priors).  CGNNI / QGNNI: 62, the plain
+ * weights, in the default build (fp32 builds with the message MLP's piecewise-linear table
+ * compiled in append it: 328).  Ask gnnd_prepared_weights_count, do not hard-code.  gnnd_decode
+ * needs this prepared buffer, not the plain weights (so does gnnd_train_fwd for V24).         */
 int gnnd_prepared_weights_count(int model, int dtype, int64_t* h_count);
 int gnnd_decode(const gnnd_graph* g, int model, int dtype, const void* d_w, const void* d_x,
                 void* d_out, int64_t batch, int32_t iters, void* stream);
@@ -227,6 +227,27 @@ int gnnd_decode(const gnnd_graph* g, int model, int dtype, const void* d_w, cons
 int gnnd_prepared_weights_count_priors(int model, int dtype, int32_t n_priors, int64_t* h_count);
 int gnnd_prepare_weights_priors(int model, int dtype, const void* d_w, void* d_prepared,
                                 const double* h_priors, int32_t n_priors, void* stream);
+/* The same tables with no host round trip: the prior list is found and read on the device, all
+ * on `stream` (memsets and kernel launches only: no host read, no synchronisation, no blocking
+ * copy), so the pair can run inside a stream capture and on batches whose p list changes.
+ * gnnd_v24_scan_priors (fp64 only: other dtypes GNND_ERR_UNSUPPORTED) reads each codeword's
+ * FIRST variable input, d_x[b * N] -- the element gnnd_decode keys a codeword's table on -- and
+ * writes the distinct values, compared bit for bit as the decoder does, NaN skipped, ASCENDING by
+ * value into d_priors[0 .. count), zeros into d_priors[count .. 64), and d_status = {count, 0}
+ * (device fp64 [64] and int32 [2]).  More than 64 distinct values: d_priors all zero and
+ * d_status = {0, 1}; no tables are built and the decode stays exact through the 128 units.  The
+ * result is a pure function of d_x (the same bits on every launch).
+ * gnnd_prepare_weights_priors_dev (fp64 V24 only: GNND_ERR_UNSUPPORTED otherwise) =
+ * gnnd_prepare_weights plus the tables of d_priors[0 .. d_status[0]) and the readout table, the
+ * same bits gnnd_prepare_weights_priors builds from that list.  The host does not know the
+ * count, so d_prepared must hold the 64-prior layout: prepared_capacity (elements) >=
+ * gnnd_prepared_weights_count_priors(.., 64), else GNND_ERR_INVALID_ARG.  Count 0: the buffer is
+ * gnnd_prepare_weights' (header 0, no tables).                                              */
+int gnnd_v24_scan_priors(const gnnd_graph* g, int dtype, const void* d_x, int64_t batch,
+                         double* d_priors, int32_t* d_status, void* stream);
+int gnnd_prepare_weights_priors_dev(int model, int dtype, const void* d_w, void* d_prepared,
+                                    int64_t prepared_capacity, const double* d_priors,
+                                    const int32_t* d_status, void* stream);
 /* The tables as the decoder evaluates them, for tests: d_y[i] = tanh(ggc1.mlp(d_u[i], d_x[i]) / 2)
  * (the prior tables hold the check step's pre-op tanh(m/2) of ggc1's output directly, as degree-7
  * series composed from the MLP's; quantum/decoder_v2_4.py:135-136) and
