@@ -201,7 +201,7 @@ extern "C" int gnnd_decode(const gnnd_graph* g, int model, int dtype, const void
 // ---------------------------------------------------------------------------------------
 #define GNND_TU_LIST(X) X(graph) X(propagate) X(decode) X(decode_v24) X(decode_qgnni) \
     X(decode_qbp) X(decode_cgnni) X(decode_cbp) X(decode_nbp) X(decode_v10) X(decode_v30) \
-    X(decode_v22) X(train) X(sample)
+    X(decode_v22) X(train) X(sample) X(osd)
 #define GNND_DECL_TU(n) extern "C" unsigned gnnd_debug_take_##n(void);
 GNND_TU_LIST(GNND_DECL_TU)
 

@@ -12,6 +12,8 @@ a custom op costs more than the 0.47 ms headline kernel, measured r02n):
   gnnd::propagate_bwd(..., grad_out, ...)  d out / d msg (HIP backward kernels)
   gnnd::decode(graph_id, model, x, iters, weights?)          fused T-iteration decoder
   gnnd::decode_out(graph_id, model, x, iters, weights?, out)  the same into `out` (mutates)
+  gnnd::osd0(graph_id, x, pred, base) -> (ehat, status)      OSD-0 post-processing of a decode
+  gnnd::osd0_out(graph_id, x, pred, base, ehat, status)       the same into its outputs (mutates)
 
 The single-codeword Tanner graph is a device object owned by libgnnd, not a tensor: ops
 take the integer id that `register_graph` hands out (TannerGraph does this on creation;
@@ -20,7 +22,7 @@ take the integer id that `register_graph` hands out (TannerGraph does this on cr
 tensor reaching an op fails in the dispatcher instead of falling back.
 """
 import weakref
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -135,4 +137,37 @@ def decode_out(graph_id: int, model: str, x: Tensor, iters: int, weights: Option
 
 @decode_out.register_fake
 def _decode_out_fake(graph_id, model, x, iters, weights, out):
+    return None
+
+
+# ---------------------------------------------------------------------------------------
+# OSD-0 post-processing
+# ---------------------------------------------------------------------------------------
+@torch.library.custom_op('gnnd::osd0', mutates_args=(), device_types='cuda')
+def osd0(graph_id: int, x: Tensor, pred: Tensor, base: str) -> Tuple[Tensor, Tensor]:
+    from . import ops
+    g = graph_of(graph_id)
+    pred = pred.contiguous()
+    ehat = torch.empty_like(pred)
+    status = torch.empty(pred.numel() // g.V, dtype=torch.int32, device=pred.device)
+    ops._osd0_impl(g, x.contiguous(), pred, base, ehat, status)
+    return ehat, status
+
+
+@osd0.register_fake
+def _osd0_fake(graph_id, x, pred, base):
+    V = _DIMS[graph_id][0]
+    return (torch.empty_like(pred, memory_format=torch.contiguous_format),
+            pred.new_empty(pred.numel() // V, dtype=torch.int32))
+
+
+@torch.library.custom_op('gnnd::osd0_out', mutates_args=('ehat', 'status'), device_types='cuda')
+def osd0_out(graph_id: int, x: Tensor, pred: Tensor, base: str, ehat: Tensor,
+             status: Tensor) -> None:
+    from . import ops
+    ops._osd0_impl(graph_of(graph_id), x.contiguous(), pred.contiguous(), base, ehat, status)
+
+
+@osd0_out.register_fake
+def _osd0_out_fake(graph_id, x, pred, base, ehat, status):
     return None

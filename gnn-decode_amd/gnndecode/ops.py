@@ -567,6 +567,80 @@ def decision_errors(graph, logical_rows, pred, y):
     return counts
 
 
+# ---------------------------------------------------------------------------------------
+# OSD-0 post-processing (gnnd_osd0): syndrome-satisfying estimates from soft outputs
+# ---------------------------------------------------------------------------------------
+def osd0(graph, x, pred, base='zero', out=None):
+    """Order-0 ordered-statistics post-processing of a decoder's soft output, one HIP launch
+    (gnnd_osd0): x [B*N(,1)] the decoder input (its check rows carry the syndrome), pred
+    [B*V(,1)] P(bit = 1) -> (ehat, status).  ehat has pred's shape and dtype and holds exactly
+    0.0 / 1.0: it satisfies the syndrome wherever status [B] (int32) is 0 and is the base vector
+    where it is 1 (syndrome outside the column space of H^T).  base 'zero': solve from the zero
+    vector with the columns ordered by pred (the usual quantum form); 'hard': solve for a
+    correction of the hard decision pred > 0.5 with the least reliable columns first (the
+    classical form).  No host sync; `out` = (ehat, status) tensors to write into."""
+    if base not in _lib.OSD_BASE:
+        raise ValueError(f"base must be 'zero' or 'hard', got {base!r}")
+    if torch.compiler.is_compiling():
+        if out is None:
+            return torch.ops.gnnd.osd0(graph.gid, x, pred, base)
+        torch.ops.gnnd.osd0_out(graph.gid, x, pred, base, out[0], out[1])
+        return out
+    _require_gpu(x, pred)
+    if x.dtype != pred.dtype:
+        raise TypeError(f'x ({x.dtype}) and pred ({pred.dtype}) must share a dtype')
+    if pred.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f'osd0 supports float32/float64, got {pred.dtype}')
+    x = x.contiguous()
+    pred = pred.contiguous()
+    B = pred.numel() // graph.V
+    if pred.numel() != B * graph.V or x.numel() != B * graph.N:
+        raise ValueError(f'pred must hold B*V and x B*N values (V = {graph.V}, N = {graph.N})')
+    if out is None:
+        out = (torch.empty_like(pred), torch.empty(B, dtype=torch.int32, device=pred.device))
+    ehat, status = out
+    _require_gpu(ehat, status)
+    if (ehat.dtype != pred.dtype or ehat.numel() != pred.numel() or not ehat.is_contiguous()
+            or status.dtype != torch.int32 or status.numel() != B or not status.is_contiguous()):
+        raise ValueError(f'out must be (contiguous {pred.dtype} [{B * graph.V}], contiguous int32 [{B}])')
+    _osd0_impl(graph, x, pred, base, ehat, status)
+    return ehat, status
+
+
+def _osd0_impl(graph, x, pred, base, ehat, status):
+    """gnnd::osd0 / gnnd::osd0_out implementation (gnndecode.library)."""
+    _lib.call('gnnd_osd0', graph.handle, dtype_code(pred.dtype), _ptr(x), _ptr(pred),
+              _lib.OSD_BASE[base], _ptr(ehat), _ptr(status), pred.numel() // graph.V,
+              current_stream(pred.device))
+
+
+def osd0_host(H, x, pred, base='zero'):
+    """The host mirror of osd0 (gnnd_osd0_host): numpy in, numpy out, no device.  H [V, C],
+    x [B*N], pred [B*V] float32 or float64 -> (ehat like pred, status int32 [B])."""
+    import numpy as np
+    from .graph import edge_list
+    if base not in _lib.OSD_BASE:
+        raise ValueError(f"base must be 'zero' or 'hard', got {base!r}")
+    H = np.asarray(H)
+    V, C = H.shape
+    pred = np.ascontiguousarray(pred)
+    if pred.dtype not in (np.float32, np.float64):
+        raise TypeError(f'osd0_host supports float32/float64, got {pred.dtype}')
+    x = np.ascontiguousarray(x, dtype=pred.dtype)
+    B = pred.size // V
+    if pred.size != B * V or x.size != B * (V + C):
+        raise ValueError(f'pred must hold B*V and x B*N values (V = {V}, N = {V + C})')
+    var, chk = edge_list(H)
+    ehat = np.empty_like(pred)
+    status = np.empty(B, np.int32)
+    P64 = ctypes.POINTER(ctypes.c_int64)
+    _lib.call('gnnd_osd0_host', var.ctypes.data_as(P64), chk.ctypes.data_as(P64), var.size, V, C,
+              _lib.F32 if pred.dtype == np.float32 else _lib.F64, x.ctypes.data, pred.ctypes.data,
+              _lib.OSD_BASE[base], ehat.ctypes.data, status.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+              B)
+    return ehat, status
+
+
 class SyndromeLossFn(torch.autograd.Function):
     """Batch-summed syndrome loss; backward scales the kernel's d loss / d pred."""
 

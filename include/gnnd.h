@@ -390,6 +390,36 @@ int gnnd_decision_errors(const gnnd_graph* g, const int32_t* d_logical, int32_t 
                          int dtype, const void* d_pred, const void* d_y, int64_t* d_counts,
                          int64_t batch, void* stream);
 
+/* ---- OSD-0 post-processing ---------------------------------------------------------------
+ * Ordered-statistics decoding of order 0 (the "OSD" of BP+OSD; for the classical codes
+ * Fossorier-Lin order-0 reprocessing): from a decoder's soft output, an estimate that satisfies
+ * the measured syndrome whenever the syndrome is in the column space of H^T.  Per codeword b,
+ * p[v] = d_pred[b*V + v], x = the decoder input in the batch layout above:
+ *   target    t[c] = (x[b*N + V + c] < 0)   (quantum inputs carry (-1)^s there, classical 0)
+ *   base      GNND_OSD_BASE_ZERO: z = 0, key[v] = p[v]               (the usual quantum form)
+ *             GNND_OSD_BASE_HARD: z[v] = (p[v] > 0.5), key[v] = -|p[v] - 0.5|, in `dtype`
+ *             a NaN p[v]: key = -inf, z[v] = 0
+ *   order     columns by descending key, ties by ascending v (decoder outputs saturate: ties
+ *             are common and the rule is part of the contract)
+ *   solve     s = t xor H^T z; walk the columns of H^T (C rows) in that order, a column being
+ *             a pivot iff some row not yet used holds a 1 in it after the reductions so far,
+ *             until rank C or the columns run out.  Reduced s zero on every non-pivot row:
+ *             e = the unique solution supported on the pivot columns, d_ehat = z xor e,
+ *             d_status = 0.  Otherwise d_ehat = z, d_status = 1.
+ * d_x [B*N], d_pred [B*V] and d_ehat [B*V] in dtype (GNND_F32 / GNND_F64; GNND_BF16:
+ * GNND_ERR_UNSUPPORTED); d_ehat holds exactly 0.0 / 1.0 and feeds gnnd_decision_errors as is;
+ * d_status [B] int32.  One launch, one wave per codeword, the bit matrix in LDS: a graph whose
+ * rows (C x (ceil(V/32) + 1) words, plus keys and order) exceed 64 KiB, or with C > 2048,
+ * returns GNND_ERR_UNSUPPORTED with nothing launched.
+ * gnnd_osd0_host is the host mirror (same definition, same bits, plain C++, no device; the
+ * graph as the edge list gnnd_graph_create takes, h_* host arrays).                          */
+typedef enum gnnd_osd_base { GNND_OSD_BASE_ZERO = 0, GNND_OSD_BASE_HARD = 1 } gnnd_osd_base;
+int gnnd_osd0(const gnnd_graph* g, int dtype, const void* d_x, const void* d_pred, int base,
+              void* d_ehat, int32_t* d_status, int64_t batch, void* stream);
+int gnnd_osd0_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                   int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                   const void* h_pred, int base, void* h_ehat, int32_t* h_status, int64_t batch);
+
 /* Adam (torch.optim.Adam update order, amsgrad/maximize off) on one flat parameter buffer of
  * n values with its two moment buffers; *d_step is the device-resident step count (double,
  * incremented by the call), so a whole training step with the update can be captured in one
