@@ -1,5 +1,6 @@
-// gnnd_osd.hip — OSD-0 post-processing (gnnd_osd0, include/gnnd.h): turns the decoders' soft
-// outputs into an estimate that satisfies the measured syndrome whenever one exists.
+// gnnd_osd.hip — OSD post-processing (gnnd_osd0 / gnnd_osd, include/gnnd.h): turns the decoders'
+// soft outputs into an estimate that satisfies the measured syndrome whenever one exists (order
+// 0), and among the higher-order candidates (combination sweep, exhaustive) the lightest one.
 #include "gnnd_common.h"
 #include "gnnd_osd_host.h"
 
@@ -18,6 +19,20 @@ GNND_DEBUG_TU(osd)
 //      bit, the first one is the pivot, its words are broadcast (one LDS address for the wave;
 //      all-zero words skipped) and XORed into every other row holding the bit;
 //   4. status = some unused row is left with s = 1; else e[pivot column of row r] = s[r].
+// gnnd_osd (osd_kernel) runs phases 1-3 through the same functions and, where 4 finds a
+// solution, a candidate phase on the reduced tile [I | T] before it writes e:
+//   5. the pivot columns are marked (bit 1 of their e byte) and the column order is compacted in
+//      place to the free list f_0 .. f_{F-1} (ballot prefix counts; a free column's slot is
+//      never after its walk position, so no second array);
+//   6. per lane three 32-bit masks over its rows (bit k = row lane + 64 k): used, s, and for a
+//      free column f its bits col_f (rpl reads of word f / 32, the same conflict-free access as
+//      phase 3).  A candidate S costs |S| + sum over the wave of popc((s ^ XOR_{f in S} col_f)
+//      & used): one __ballot + popcount when C <= 64, else a DPP / shuffle add.  Combination
+//      sweep: all singles, then the pairs of the first lambda free columns; exhaustive: the
+//      2^lambda subsets in Gray-code order, one column XORed into a running mask per step.  The
+//      best (cost, index) stays wave-uniform in scalars, ties to the lowest index;
+//   7. e is written once, for the chosen candidate: its free columns and the pivots of the rows
+//      its mask leaves set.
 // ---------------------------------------------------------------------------------------
 constexpr int kOsdMaxRowsPerLane = 32;      // `used` is one 32-bit mask per lane: C <= 2048
 constexpr size_t kOsdLdsLimit = 64 * 1024;  // dynamic LDS of one workgroup without an opt-in
@@ -58,6 +73,110 @@ __device__ __forceinline__ void osd_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// one wave's tile
+template <typename T>
+struct OsdTile {
+    uint32_t* A;
+    T* key;
+    uint16_t* order;
+    uint16_t* piv;
+    uint8_t* e;
+    __device__ __forceinline__ OsdTile(char* tile, const OsdPlan& pl)
+        : A((uint32_t*)tile), key((T*)(tile + pl.off_key)),
+          order((uint16_t*)(tile + pl.off_order)), piv((uint16_t*)(tile + pl.off_piv)),
+          e((uint8_t*)(tile + pl.off_e)) {}
+};
+
+// ---- phase 1: base vector, ordering key, column order by counting ----
+template <typename T>
+__device__ __forceinline__ void osd_keys_and_order(const OsdTile<T>& t, int V, int hard,
+                                                   const T* __restrict__ pb, int lane) {
+    for (int v = lane; v < V; v += 64) {
+        const T p = pb[v];
+        const T d = p - T(0.5);
+        const T k = hard ? -g_abs(d) : p;
+        t.key[v] = p != p ? -(T)INFINITY : k;
+        t.e[v] = (uint8_t)(hard && p > T(0.5));
+    }
+    osd_wave_sync();
+    for (int v = lane; v < V; v += 64) {
+        const T kv = t.key[v];
+        int rank = 0;
+        for (int u = 0; u < V; ++u) {
+            const T ku = t.key[u];
+            rank += (ku > kv) | ((ku == kv) & (u < v));
+        }
+        t.order[GNND_DIDX(rank, V, GNND_DBG_LDS_POS)] = (uint16_t)v;
+    }
+}
+
+// ---- phase 2: A = H^T rows with the residual syndrome ----
+template <typename T>
+__device__ __forceinline__ void osd_build_rows(const OsdTile<T>& t, const GraphView& g,
+                                               const OsdPlan& pl, const T* __restrict__ xchk,
+                                               int lane) {
+    const int C = g.C, S = pl.stride, syn = pl.words;
+    for (int k = 0; k < pl.rpl; ++k) {
+        const int r = lane + 64 * k;
+        if (r >= C) break;
+        uint32_t* row = t.A + (size_t)r * S;
+        for (int w = 0; w < S; ++w) row[w] = 0;
+        int par = xchk[r] < T(0);
+        for (int i = g.chk_ptr[r]; i < g.chk_ptr[r + 1]; ++i) {
+            const int e = GNND_DIDX(g.chk_edge[GNND_DIDX(i, g.E, GNND_DBG_SLOT)], g.E, GNND_DBG_SLOT);
+            const int v = GNND_DIDX((int)(g.edge_vc[e] & 0xffffu), g.V, GNND_DBG_VAR);
+            row[v >> 5] |= 1u << (v & 31);
+            par ^= t.e[v];
+        }
+        row[syn] = (uint32_t)par;
+    }
+    osd_wave_sync();
+}
+
+// ---- phase 3: Gauss-Jordan over the ordered columns; returns the lane's pivot-row mask
+// (bit k: row lane + 64 k is a pivot row) ----
+template <typename T>
+__device__ __forceinline__ uint32_t osd_eliminate(const OsdTile<T>& t, const OsdPlan& pl, int V,
+                                                  int C, int lane) {
+    const int S = pl.stride;
+    uint32_t* A = t.A;
+    uint32_t used = 0;
+    int rank = 0;
+    for (int pos = 0; pos < V && rank < C; ++pos) {
+        const int j = GNND_DIDX((int)t.order[pos], V, GNND_DBG_VAR);
+        const int wj = j >> 5;
+        const uint32_t bj = 1u << (j & 31);
+        uint32_t hit = 0;               // bit k: row lane + 64 k holds column j
+        int prow = -1;
+        for (int k = 0; k < pl.rpl; ++k) {
+            const int r = lane + 64 * k;
+            const bool has = r < C && (A[(size_t)r * S + wj] & bj);
+            hit |= (uint32_t)has << k;
+            if (prow < 0) {
+                const unsigned long long m = __ballot(has && !((used >> k) & 1u));
+                if (m) prow = 64 * k + __builtin_ctzll(m);
+            }
+        }
+        if (prow < 0) continue;
+        GNND_DCHECK(prow < C, GNND_DBG_NODE);
+        if (lane == (prow & 63)) {
+            used |= 1u << (prow >> 6);
+            hit &= ~(1u << (prow >> 6));
+            t.piv[prow] = (uint16_t)j;
+        }
+        ++rank;
+        const uint32_t* prw = A + (size_t)prow * S;
+        for (int w = 0; w < S; ++w) {
+            const uint32_t pw = __builtin_amdgcn_readfirstlane(prw[w]);
+            if (pw == 0) continue;
+            for (int k = 0; k < pl.rpl; ++k)
+                if ((hit >> k) & 1u) A[(size_t)(lane + 64 * k) * S + w] ^= pw;
+        }
+        osd_wave_sync();
+    }
+    return used;
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256)
 osd0_kernel(GraphView g, OsdPlan pl, int hard, const T* __restrict__ x,
@@ -67,86 +186,16 @@ osd0_kernel(GraphView g, OsdPlan pl, int hard, const T* __restrict__ x,
     const int V = g.V, C = g.C, N = g.N;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int S = pl.stride, syn = pl.words;
-    char* tile = smem + (size_t)wave * pl.wave_bytes;
-    uint32_t* A = (uint32_t*)tile;
-    T* s_key = (T*)(tile + pl.off_key);
-    uint16_t* s_order = (uint16_t*)(tile + pl.off_order);
-    uint16_t* s_piv = (uint16_t*)(tile + pl.off_piv);
-    uint8_t* s_e = (uint8_t*)(tile + pl.off_e);
+    const OsdTile<T> t(smem + (size_t)wave * pl.wave_bytes, pl);
+    uint32_t* A = t.A;
+    uint16_t* s_piv = t.piv;
+    uint8_t* s_e = t.e;
 
     for (int64_t b = (int64_t)blockIdx.x * pl.waves + wave; b < B;
          b += (int64_t)gridDim.x * pl.waves) {
-        const T* pb = pred + b * V;
-        // ---- base vector and ordering key ----
-        for (int v = lane; v < V; v += 64) {
-            const T p = pb[v];
-            const T d = p - T(0.5);
-            const T k = hard ? -g_abs(d) : p;
-            s_key[v] = p != p ? -(T)INFINITY : k;
-            s_e[v] = (uint8_t)(hard && p > T(0.5));
-        }
-        osd_wave_sync();
-        // ---- column order by counting ----
-        for (int v = lane; v < V; v += 64) {
-            const T kv = s_key[v];
-            int rank = 0;
-            for (int u = 0; u < V; ++u) {
-                const T ku = s_key[u];
-                rank += (ku > kv) | ((ku == kv) & (u < v));
-            }
-            s_order[GNND_DIDX(rank, V, GNND_DBG_LDS_POS)] = (uint16_t)v;
-        }
-        // ---- A = H^T rows with the residual syndrome ----
-        for (int k = 0; k < pl.rpl; ++k) {
-            const int r = lane + 64 * k;
-            if (r >= C) break;
-            uint32_t* row = A + (size_t)r * S;
-            for (int w = 0; w < S; ++w) row[w] = 0;
-            int par = x[b * N + V + r] < T(0);
-            for (int i = g.chk_ptr[r]; i < g.chk_ptr[r + 1]; ++i) {
-                const int e = GNND_DIDX(g.chk_edge[GNND_DIDX(i, g.E, GNND_DBG_SLOT)], g.E, GNND_DBG_SLOT);
-                const int v = GNND_DIDX((int)(g.edge_vc[e] & 0xffffu), V, GNND_DBG_VAR);
-                row[v >> 5] |= 1u << (v & 31);
-                par ^= s_e[v];
-            }
-            row[syn] = (uint32_t)par;
-        }
-        osd_wave_sync();
-        // ---- Gauss-Jordan over the ordered columns ----
-        uint32_t used = 0;                  // bit k: row lane + 64 k is a pivot row
-        int rank = 0;
-        for (int pos = 0; pos < V && rank < C; ++pos) {
-            const int j = GNND_DIDX((int)s_order[pos], V, GNND_DBG_VAR);
-            const int wj = j >> 5;
-            const uint32_t bj = 1u << (j & 31);
-            uint32_t hit = 0;               // bit k: row lane + 64 k holds column j
-            int prow = -1;
-            for (int k = 0; k < pl.rpl; ++k) {
-                const int r = lane + 64 * k;
-                const bool has = r < C && (A[(size_t)r * S + wj] & bj);
-                hit |= (uint32_t)has << k;
-                if (prow < 0) {
-                    const unsigned long long m = __ballot(has && !((used >> k) & 1u));
-                    if (m) prow = 64 * k + __builtin_ctzll(m);
-                }
-            }
-            if (prow < 0) continue;
-            GNND_DCHECK(prow < C, GNND_DBG_NODE);
-            if (lane == (prow & 63)) {
-                used |= 1u << (prow >> 6);
-                hit &= ~(1u << (prow >> 6));
-                s_piv[prow] = (uint16_t)j;
-            }
-            ++rank;
-            const uint32_t* prw = A + (size_t)prow * S;
-            for (int w = 0; w < S; ++w) {
-                const uint32_t pw = __builtin_amdgcn_readfirstlane(prw[w]);
-                if (pw == 0) continue;
-                for (int k = 0; k < pl.rpl; ++k)
-                    if ((hit >> k) & 1u) A[(size_t)(lane + 64 * k) * S + w] ^= pw;
-            }
-            osd_wave_sync();
-        }
+        osd_keys_and_order(t, V, hard, pred + b * V, lane);
+        osd_build_rows(t, g, pl, x + b * N + V, lane);
+        const uint32_t used = osd_eliminate(t, pl, V, C, lane);
         // ---- solution ----
         int bad = 0;
         for (int k = 0; k < pl.rpl; ++k) {
@@ -168,17 +217,187 @@ osd0_kernel(GraphView g, OsdPlan pl, int hard, const T* __restrict__ x,
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// higher-order candidates (phases 5-7)
+// ---------------------------------------------------------------------------------------
+template <int CTRL> __device__ __forceinline__ int osd_dpp(int v) {
+    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false);
+}
+// sum over the 64 lanes (all active), the same value in every lane
+__device__ __forceinline__ int osd_wave_sum(int v) {
+    v += osd_dpp<0xB1>(v);     // quad_perm [1,0,3,2]
+    v += osd_dpp<0x4E>(v);     // quad_perm [2,3,0,1]
+    v += osd_dpp<0x141>(v);    // row_half_mirror
+    v += osd_dpp<0x140>(v);    // row_mirror
+    v += __shfl_xor(v, 16);
+    v += __shfl_xor(v, 32);
+    return v;
+}
+// number of set bits of a per-lane row mask over the wave, wave-uniform; `one`: one row per lane
+__device__ __forceinline__ int osd_weight(uint32_t m, bool one) {
+    if (one) return __popcll(__ballot(m & 1u));
+    return __builtin_amdgcn_readfirstlane(osd_wave_sum(__popc(m)));
+}
+// bits of column f over the lane's rows (bit k: row lane + 64 k)
+__device__ __forceinline__ uint32_t osd_col_mask(const uint32_t* A, int S, int C, int rpl,
+                                                 int lane, int f) {
+    const int wf = f >> 5, sh = f & 31;
+    uint32_t m = 0;
+    for (int k = 0; k < rpl; ++k) {
+        const int r = lane + 64 * k;
+        if (r < C) m |= ((A[(size_t)r * S + wf] >> sh) & 1u) << k;
+    }
+    return m;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+osd_kernel(GraphView g, OsdPlan pl, int hard, int method, int order, const T* __restrict__ x,
+           const T* __restrict__ pred, T* __restrict__ ehat, int32_t* __restrict__ status,
+           int32_t* __restrict__ choice, int64_t B) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int V = g.V, C = g.C, N = g.N;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int S = pl.stride, syn = pl.words, rpl = pl.rpl;
+    const bool one = rpl == 1;
+    const OsdTile<T> t(smem + (size_t)wave * pl.wave_bytes, pl);
+    const uint32_t* A = t.A;
+    uint16_t* s_order = t.order;
+    uint8_t* s_e = t.e;
+
+    for (int64_t b = (int64_t)blockIdx.x * pl.waves + wave; b < B;
+         b += (int64_t)gridDim.x * pl.waves) {
+        osd_keys_and_order(t, V, hard, pred + b * V, lane);
+        osd_build_rows(t, g, pl, x + b * N + V, lane);
+        const uint32_t used = osd_eliminate(t, pl, V, C, lane);
+        uint32_t smask = 0;                 // bit k: reduced s of row lane + 64 k
+        for (int k = 0; k < rpl; ++k) {
+            const int r = lane + 64 * k;
+            if (r < C) smask |= (A[(size_t)r * S + syn] & 1u) << k;
+        }
+        const bool fail = __ballot((smask & ~used) != 0) != 0;
+        int best_idx = 0;
+        if (!fail) {
+            uint32_t fm = smask;            // the chosen candidate's s xor its columns
+            if (method != GNND_OSD_0) {
+                // ---- free list: mark the pivot columns, compact the order in place ----
+                for (int k = 0; k < rpl; ++k)
+                    if ((used >> k) & 1u)
+                        s_e[GNND_DIDX((int)t.piv[lane + 64 * k], V, GNND_DBG_VAR)] |= 2;
+                osd_wave_sync();
+                int F = 0;
+                for (int base = 0; base < V; base += 64) {
+                    const int pos = base + lane;
+                    int v = 0;
+                    bool fr = false;
+                    if (pos < V) {
+                        v = GNND_DIDX((int)s_order[pos], V, GNND_DBG_VAR);
+                        fr = !(s_e[v] & 2);
+                    }
+                    const unsigned long long m = __ballot(fr);
+                    osd_wave_sync();        // every slot of the chunk read before one is rewritten
+                    if (fr)
+                        s_order[GNND_DIDX(F + __popcll(m & ((1ull << lane) - 1)), pos + 1,
+                                          GNND_DBG_LDS_POS)] = (uint16_t)v;
+                    F += __popcll(m);
+                }
+                osd_wave_sync();
+                GNND_DCHECK(F <= V, GNND_DBG_LDS_POS);
+                // ---- candidates ----
+                int best = osd_weight(smask & used, one);
+                const int lam = order < F ? order : F;
+                if (method == GNND_OSD_CS) {
+                    int ba = -1, bb = -1;
+                    for (int i = 0; i < F; ++i) {
+                        const int f = GNND_DIDX((int)s_order[i], V, GNND_DBG_VAR);
+                        const uint32_t m = smask ^ osd_col_mask(A, S, C, rpl, lane, f);
+                        const int c = 1 + osd_weight(m & used, one);
+                        if (c < best) { best = c; best_idx = 1 + i; ba = i; }
+                    }
+                    int idx = 1 + F;
+                    for (int a = 0; a + 1 < lam; ++a) {
+                        const int fa = GNND_DIDX((int)s_order[a], V, GNND_DBG_VAR);
+                        const uint32_t ma = smask ^ osd_col_mask(A, S, C, rpl, lane, fa);
+                        for (int q = a + 1; q < lam; ++q, ++idx) {
+                            const int fq = GNND_DIDX((int)s_order[q], V, GNND_DBG_VAR);
+                            const uint32_t m = ma ^ osd_col_mask(A, S, C, rpl, lane, fq);
+                            const int c = 2 + osd_weight(m & used, one);
+                            if (c < best) { best = c; best_idx = idx; ba = a; bb = q; }
+                        }
+                    }
+                    if (ba >= 0) {
+                        const int fa = GNND_DIDX((int)s_order[ba], V, GNND_DBG_VAR);
+                        fm ^= osd_col_mask(A, S, C, rpl, lane, fa);
+                        if (lane == 0) s_e[fa] ^= 1;
+                    }
+                    if (bb >= 0) {
+                        const int fq = GNND_DIDX((int)s_order[bb], V, GNND_DBG_VAR);
+                        fm ^= osd_col_mask(A, S, C, rpl, lane, fq);
+                        if (lane == 0) s_e[fq] ^= 1;
+                    }
+                } else {
+                    uint32_t run = smask;
+                    int gray = 0;           // the subset visited: Gray code of the step
+                    for (int i = 1; i < (1 << lam); ++i) {
+                        const int bit = __builtin_ctz(i);
+                        gray ^= 1 << bit;
+                        const int f = GNND_DIDX((int)s_order[bit], V, GNND_DBG_VAR);
+                        run ^= osd_col_mask(A, S, C, rpl, lane, f);
+                        const int c = __popc(gray) + osd_weight(run & used, one);
+                        if (c < best || (c == best && gray < best_idx)) { best = c; best_idx = gray; }
+                    }
+                    for (int i = 0; i < lam; ++i)
+                        if ((best_idx >> i) & 1) {
+                            const int f = GNND_DIDX((int)s_order[i], V, GNND_DBG_VAR);
+                            fm ^= osd_col_mask(A, S, C, rpl, lane, f);
+                            if (lane == 0) s_e[f] ^= 1;
+                        }
+                }
+            }
+            // ---- solution: the pivots of the rows the chosen mask leaves set ----
+            for (int k = 0; k < rpl; ++k)
+                if ((used >> k) & (fm >> k) & 1u)
+                    s_e[GNND_DIDX((int)t.piv[lane + 64 * k], V, GNND_DBG_VAR)] ^= 1;
+        }
+        osd_wave_sync();
+        T* eb = ehat + b * V;
+        for (int v = lane; v < V; v += 64) eb[v] = (s_e[v] & 1) ? T(1) : T(0);
+        if (lane == 0) {
+            status[b] = fail ? 1 : 0;
+            if (choice) choice[b] = best_idx;
+        }
+        osd_wave_sync();                    // tile reads done before the next codeword's writes
+    }
+}
+
+static unsigned osd_blocks(const OsdPlan& pl, int64_t B) {
+    const int64_t want = (B + pl.waves - 1) / pl.waves;
+    const int64_t cap = 8192 / pl.waves;                  // 32 waves per CU, grid-stride
+    return (unsigned)(want < cap ? want : cap);
+}
+
 template <typename T>
 static int launch_osd0(const gnnd_graph* g, const void* x, const void* pred, int base, void* ehat,
                        int32_t* status, int64_t B, hipStream_t st) {
     const GraphView& v = g->view;
     const OsdPlan pl = osd_plan(v.V, v.C, sizeof(T));
     if (pl.waves == 0) return GNND_ERR_UNSUPPORTED;
-    const int64_t want = (B + pl.waves - 1) / pl.waves;
-    const int64_t cap = 8192 / pl.waves;                  // 32 waves per CU, grid-stride
-    const int64_t blocks = want < cap ? want : cap;
-    osd0_kernel<T><<<(unsigned)blocks, 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
+    osd0_kernel<T><<<osd_blocks(pl, B), 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
         v, pl, base == GNND_OSD_BASE_HARD, (const T*)x, (const T*)pred, (T*)ehat, status, B);
+    GNND_LAUNCH_CHECK();
+    return GNND_OK;
+}
+
+template <typename T>
+static int launch_osd(const gnnd_graph* g, const void* x, const void* pred, int base, int method,
+                      int order, void* ehat, int32_t* status, int32_t* choice, int64_t B,
+                      hipStream_t st) {
+    const GraphView& v = g->view;
+    const OsdPlan pl = osd_plan(v.V, v.C, sizeof(T));
+    if (pl.waves == 0) return GNND_ERR_UNSUPPORTED;
+    osd_kernel<T><<<osd_blocks(pl, B), 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
+        v, pl, base == GNND_OSD_BASE_HARD, method, order, (const T*)x, (const T*)pred, (T*)ehat,
+        status, choice, B);
     GNND_LAUNCH_CHECK();
     return GNND_OK;
 }
@@ -203,4 +422,30 @@ extern "C" int gnnd_osd0_host(const int64_t* h_var, const int64_t* h_chk, int64_
                               int64_t batch) {
     return gnnd_osd0_host_checked(h_var, h_chk, num_edges, num_var, num_chk, dtype, h_x, h_pred,
                                   base, h_ehat, h_status, batch);
+}
+
+extern "C" int gnnd_osd(const gnnd_graph* g, int dtype, const void* d_x, const void* d_pred,
+                        int base, int method, int32_t order, void* d_ehat, int32_t* d_status,
+                        int32_t* d_choice, int64_t batch, void* stream) {
+    if (!g || batch < 0) return GNND_ERR_INVALID_ARG;
+    if (base != GNND_OSD_BASE_ZERO && base != GNND_OSD_BASE_HARD) return GNND_ERR_INVALID_ARG;
+    if (!gnnd_osd_order_ok(method, order)) return GNND_ERR_INVALID_ARG;
+    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
+    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    if (batch == 0) return GNND_OK;
+    if (!d_x || !d_pred || !d_ehat || !d_status) return GNND_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == GNND_F32)
+        return launch_osd<float>(g, d_x, d_pred, base, method, order, d_ehat, d_status, d_choice,
+                                 batch, st);
+    return launch_osd<double>(g, d_x, d_pred, base, method, order, d_ehat, d_status, d_choice,
+                              batch, st);
+}
+
+extern "C" int gnnd_osd_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                             int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                             const void* h_pred, int base, int method, int32_t order,
+                             void* h_ehat, int32_t* h_status, int32_t* h_choice, int64_t batch) {
+    return gnnd_osd_host_checked(h_var, h_chk, num_edges, num_var, num_chk, dtype, h_x, h_pred,
+                                 base, method, order, h_ehat, h_status, h_choice, batch);
 }

@@ -1,8 +1,11 @@
-// gnnd_osd_host.h — host mirror of gnnd_osd0 (include/gnnd.h): order-0 ordered-statistics
-// post-processing in plain C++.  No HIP types: a plain host compiler builds it, so a stand-alone
-// program can run it under host sanitizers (tools/osd_host_check.cpp).  Same definition as the
+// gnnd_osd_host.h — host mirror of gnnd_osd0 and gnnd_osd (include/gnnd.h): ordered-statistics
+// post-processing (order 0, combination sweep, exhaustive) in plain C++.  No HIP types: a plain
+// host compiler builds it, so a stand-alone program can run it under host sanitizers
+// (tools/osd_host_check.cpp).  Same definition as the
 // kernel in gnnd_osd.hip, bit for bit: columns by descending key (ties: ascending v), Gauss-Jordan
-// over the C rows of H^T with the residual syndrome as one more column, solution on the pivots.
+// over the C rows of H^T with the residual syndrome as one more column, solution on the pivots;
+// for gnnd_osd the candidates over the free columns follow, lightest first, ties to the lowest
+// candidate index.
 #pragma once
 #include <stdint.h>
 #include <math.h>
@@ -11,10 +14,28 @@
 #include <vector>
 #include "../../include/gnnd.h"
 
+// method and order of gnnd_osd within the contract's limits
+inline bool gnnd_osd_order_ok(int method, int32_t order) {
+    if (order < 0) return false;
+    if (method == GNND_OSD_0) return true;
+    if (method == GNND_OSD_CS) return order <= 64;
+    return method == GNND_OSD_E && order <= 12;
+}
+
+// weight of (s xor c) over the pivot rows; c may be null
+inline int gnnd_osd_host_weight(const uint64_t* s, const uint64_t* c, const uint64_t* c2,
+                                const uint64_t* used, int RW) {
+    int n = 0;
+    for (int w = 0; w < RW; ++w)
+        n += __builtin_popcountll((s[w] ^ (c ? c[w] : 0) ^ (c2 ? c2[w] : 0)) & used[w]);
+    return n;
+}
+
+// choice may be null; method GNND_OSD_0 is gnnd_osd0_host
 template <typename T>
-int gnnd_osd0_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges, int V,
-                        int C, const T* x, const T* pred, int base, T* ehat, int32_t* status,
-                        int64_t batch) {
+int gnnd_osd_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges, int V,
+                       int C, const T* x, const T* pred, int base, int method, int order_arg,
+                       T* ehat, int32_t* status, int32_t* choice, int64_t batch) {
     for (int64_t e = 0; e < num_edges; ++e)
         if (h_var[e] < 0 || h_var[e] >= V || h_chk[e] < 0 || h_chk[e] >= C) return GNND_ERR_GRAPH;
     // rows of H^T, bit-packed: words [0, W) hold the V columns, bit V the syndrome
@@ -25,7 +46,11 @@ int gnnd_osd0_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num_
     const int N = V + C;
     std::vector<T> key(V);
     std::vector<int> order(V), piv_col(C);
-    std::vector<uint8_t> z(V), used(C);
+    std::vector<uint8_t> z(V), used(C), is_piv(V);
+    // candidates: bits over the C rows, 64 per word: the pivot rows, s, the free columns
+    const int RW = (C + 63) / 64;
+    std::vector<int> free_col;
+    std::vector<uint64_t> usedw(RW), sw(RW), colw, sub;
     for (int64_t b = 0; b < batch; ++b) {
         const T* p = pred + b * V;
         const T* xc = x + b * N + V;
@@ -71,13 +96,86 @@ int gnnd_osd0_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num_
         int bad = 0;
         for (int c = 0; c < C; ++c)
             bad |= !used[c] && ((A[(size_t)c * W + (V >> 6)] >> (V & 63)) & 1);
-        if (!bad)
+        int best_idx = 0;
+        if (!bad && method != GNND_OSD_0) {
+            std::fill(is_piv.begin(), is_piv.end(), 0);
+            std::fill(usedw.begin(), usedw.end(), 0);
+            std::fill(sw.begin(), sw.end(), 0);
+            for (int c = 0; c < C; ++c) {
+                if (used[c]) {
+                    is_piv[piv_col[c]] = 1;
+                    usedw[c >> 6] |= (uint64_t)1 << (c & 63);
+                }
+                sw[c >> 6] |= ((A[(size_t)c * W + (V >> 6)] >> (V & 63)) & 1) << (c & 63);
+            }
+            free_col.clear();
+            for (int pos = 0; pos < V; ++pos)
+                if (!is_piv[order[pos]]) free_col.push_back(order[pos]);
+            const int F = (int)free_col.size();
+            const int lam = order_arg < F ? order_arg : F;
+            colw.assign((size_t)F * RW, 0);
+            for (int i = 0; i < F; ++i) {
+                const int f = free_col[i];
+                for (int c = 0; c < C; ++c)
+                    colw[(size_t)i * RW + (c >> 6)] |=
+                        ((A[(size_t)c * W + (f >> 6)] >> (f & 63)) & 1) << (c & 63);
+            }
+            int best = gnnd_osd_host_weight(sw.data(), nullptr, nullptr, usedw.data(), RW);
+            if (method == GNND_OSD_CS) {
+                int ba = -1, bb = -1;
+                for (int i = 0; i < F; ++i) {
+                    const int c = 1 + gnnd_osd_host_weight(sw.data(), &colw[(size_t)i * RW], nullptr,
+                                                           usedw.data(), RW);
+                    if (c < best) { best = c; best_idx = 1 + i; ba = i; }
+                }
+                int idx = 1 + F;
+                for (int a = 0; a < lam; ++a)
+                    for (int q = a + 1; q < lam; ++q, ++idx) {
+                        const int c = 2 + gnnd_osd_host_weight(sw.data(), &colw[(size_t)a * RW],
+                                                               &colw[(size_t)q * RW], usedw.data(), RW);
+                        if (c < best) { best = c; best_idx = idx; ba = a; bb = q; }
+                    }
+                for (int i : {ba, bb})
+                    if (i >= 0) {
+                        z[free_col[i]] ^= 1;
+                        for (int w = 0; w < RW; ++w) sw[w] ^= colw[(size_t)i * RW + w];
+                    }
+            } else {
+                // sub[m] = XOR of the columns in subset m, from the subset without m's lowest bit
+                sub.assign(((size_t)1 << lam) * RW, 0);
+                for (int m = 1; m < (1 << lam); ++m) {
+                    const int low = __builtin_ctz(m);
+                    for (int w = 0; w < RW; ++w)
+                        sub[(size_t)m * RW + w] =
+                            sub[(size_t)(m & (m - 1)) * RW + w] ^ colw[(size_t)low * RW + w];
+                    const int c = __builtin_popcount(m) +
+                                  gnnd_osd_host_weight(sw.data(), &sub[(size_t)m * RW], nullptr,
+                                                       usedw.data(), RW);
+                    if (c < best) { best = c; best_idx = m; }
+                }
+                for (int i = 0; i < lam; ++i)
+                    if ((best_idx >> i) & 1) z[free_col[i]] ^= 1;
+                for (int w = 0; w < RW; ++w) sw[w] ^= sub[(size_t)best_idx * RW + w];
+            }
+            for (int c = 0; c < C; ++c)
+                if (used[c]) z[piv_col[c]] ^= (uint8_t)((sw[c >> 6] >> (c & 63)) & 1);
+        } else if (!bad) {
             for (int c = 0; c < C; ++c)
                 if (used[c]) z[piv_col[c]] ^= (uint8_t)((A[(size_t)c * W + (V >> 6)] >> (V & 63)) & 1);
+        }
         for (int v = 0; v < V; ++v) eb[v] = z[v] ? T(1) : T(0);
         status[b] = bad;
+        if (choice) choice[b] = best_idx;
     }
     return GNND_OK;
+}
+
+template <typename T>
+int gnnd_osd0_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges, int V,
+                        int C, const T* x, const T* pred, int base, T* ehat, int32_t* status,
+                        int64_t batch) {
+    return gnnd_osd_host_impl<T>(h_var, h_chk, num_edges, V, C, x, pred, base, GNND_OSD_0, 0, ehat,
+                                 status, nullptr, batch);
 }
 
 inline int gnnd_osd0_host_checked(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
@@ -98,4 +196,26 @@ inline int gnnd_osd0_host_checked(const int64_t* h_var, const int64_t* h_chk, in
     return gnnd_osd0_host_impl<double>(h_var, h_chk, num_edges, num_var, num_chk,
                                        (const double*)h_x, (const double*)h_pred, base,
                                        (double*)h_ehat, h_status, batch);
+}
+
+inline int gnnd_osd_host_checked(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                                 int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                                 const void* h_pred, int base, int method, int32_t order,
+                                 void* h_ehat, int32_t* h_status, int32_t* h_choice,
+                                 int64_t batch) {
+    if (!h_var || !h_chk || num_edges <= 0 || num_var <= 0 || num_chk <= 0 || batch < 0)
+        return GNND_ERR_INVALID_ARG;
+    if (base != GNND_OSD_BASE_ZERO && base != GNND_OSD_BASE_HARD) return GNND_ERR_INVALID_ARG;
+    if (!gnnd_osd_order_ok(method, order)) return GNND_ERR_INVALID_ARG;
+    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
+    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    if (batch == 0) return GNND_OK;
+    if (!h_x || !h_pred || !h_ehat || !h_status) return GNND_ERR_INVALID_ARG;
+    if (dtype == GNND_F32)
+        return gnnd_osd_host_impl<float>(h_var, h_chk, num_edges, num_var, num_chk,
+                                         (const float*)h_x, (const float*)h_pred, base, method,
+                                         order, (float*)h_ehat, h_status, h_choice, batch);
+    return gnnd_osd_host_impl<double>(h_var, h_chk, num_edges, num_var, num_chk,
+                                      (const double*)h_x, (const double*)h_pred, base, method,
+                                      order, (double*)h_ehat, h_status, h_choice, batch);
 }

@@ -14,6 +14,8 @@ a custom op costs more than the 0.47 ms headline kernel, measured r02n):
   gnnd::decode_out(graph_id, model, x, iters, weights?, out)  the same into `out` (mutates)
   gnnd::osd0(graph_id, x, pred, base) -> (ehat, status)      OSD-0 post-processing of a decode
   gnnd::osd0_out(graph_id, x, pred, base, ehat, status)       the same into its outputs (mutates)
+  gnnd::osd(graph_id, x, pred, base, method, order) -> (ehat, status, choice)   higher-order OSD
+  gnnd::osd_out(graph_id, x, pred, base, method, order, ehat, status, choice)   the same, mutating
 
 The single-codeword Tanner graph is a device object owned by libgnnd, not a tensor: ops
 take the integer id that `register_graph` hands out (TannerGraph does this on creation;
@@ -170,4 +172,43 @@ def osd0_out(graph_id: int, x: Tensor, pred: Tensor, base: str, ehat: Tensor,
 
 @osd0_out.register_fake
 def _osd0_out_fake(graph_id, x, pred, base, ehat, status):
+    return None
+
+
+# ---------------------------------------------------------------------------------------
+# higher-order OSD post-processing (combination sweep, exhaustive)
+# ---------------------------------------------------------------------------------------
+@torch.library.custom_op('gnnd::osd', mutates_args=(), device_types='cuda')
+def osd(graph_id: int, x: Tensor, pred: Tensor, base: str, method: str,
+        order: int) -> Tuple[Tensor, Tensor, Tensor]:
+    from . import ops
+    g = graph_of(graph_id)
+    pred = pred.contiguous()
+    B = pred.numel() // g.V
+    ehat = torch.empty_like(pred)
+    status = torch.empty(B, dtype=torch.int32, device=pred.device)
+    choice = torch.empty(B, dtype=torch.int32, device=pred.device)
+    ops._osd_impl(g, x.contiguous(), pred, base, method, order, ehat, status, choice)
+    return ehat, status, choice
+
+
+@osd.register_fake
+def _osd_fake(graph_id, x, pred, base, method, order):
+    V = _DIMS[graph_id][0]
+    B = pred.numel() // V
+    return (torch.empty_like(pred, memory_format=torch.contiguous_format),
+            pred.new_empty(B, dtype=torch.int32), pred.new_empty(B, dtype=torch.int32))
+
+
+@torch.library.custom_op('gnnd::osd_out', mutates_args=('ehat', 'status', 'choice'),
+                         device_types='cuda')
+def osd_out(graph_id: int, x: Tensor, pred: Tensor, base: str, method: str, order: int,
+            ehat: Tensor, status: Tensor, choice: Tensor) -> None:
+    from . import ops
+    ops._osd_impl(graph_of(graph_id), x.contiguous(), pred.contiguous(), base, method, order,
+                  ehat, status, choice)
+
+
+@osd_out.register_fake
+def _osd_out_fake(graph_id, x, pred, base, method, order, ehat, status, choice):
     return None

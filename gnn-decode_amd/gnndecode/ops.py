@@ -641,6 +641,102 @@ def osd0_host(H, x, pred, base='zero'):
     return ehat, status
 
 
+# ---------------------------------------------------------------------------------------
+# higher-order OSD post-processing (gnnd_osd): the lightest of the combination-sweep or
+# exhaustive candidates on top of OSD-0
+# ---------------------------------------------------------------------------------------
+def _osd_check_method(base, method, order):
+    if base not in _lib.OSD_BASE:
+        raise ValueError(f"base must be 'zero' or 'hard', got {base!r}")
+    if method not in _lib.OSD_METHOD:
+        raise ValueError(f"method must be 'osd0', 'cs' or 'e', got {method!r}")
+    limit = {'osd0': 2 ** 31 - 1, 'cs': 64, 'e': 12}[method]
+    if not isinstance(order, int) or not 0 <= order <= limit:
+        raise ValueError(f'order must be an integer in [0, {limit}] for method {method!r}, got {order!r}')
+
+
+def osd(graph, x, pred, base='zero', method='cs', order=10, out=None):
+    """Ordered-statistics post-processing of order > 0, one HIP launch (gnnd_osd): as osd0, then
+    among a fixed list of further syndrome-satisfying candidates over the free (non-pivot)
+    columns the one of least weight, ties to the lowest candidate index (include/gnnd.h).
+    method 'osd0': the OSD-0 solution alone; 'cs' (combination sweep): every single free column,
+    then the pairs of the first min(order, F) of them, order <= 64; 'e' (exhaustive): the
+    2^min(order, F) subsets of the first free columns, order <= 12.  -> (ehat, status, choice):
+    ehat and status as osd0, choice [B] int32 the chosen candidate's index (0: the OSD-0
+    solution, and where status is 1).  No host sync; `out` = (ehat, status, choice) tensors to
+    write into, or (ehat, status) to skip the choice (returned as None)."""
+    _osd_check_method(base, method, order)
+    if torch.compiler.is_compiling():
+        if out is None:
+            return torch.ops.gnnd.osd(graph.gid, x, pred, base, method, order)
+        if len(out) != 3 or out[2] is None:
+            raise ValueError('traced osd needs out = (ehat, status, choice)')
+        torch.ops.gnnd.osd_out(graph.gid, x, pred, base, method, order, out[0], out[1], out[2])
+        return out
+    _require_gpu(x, pred)
+    if x.dtype != pred.dtype:
+        raise TypeError(f'x ({x.dtype}) and pred ({pred.dtype}) must share a dtype')
+    if pred.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f'osd supports float32/float64, got {pred.dtype}')
+    x = x.contiguous()
+    pred = pred.contiguous()
+    B = pred.numel() // graph.V
+    if pred.numel() != B * graph.V or x.numel() != B * graph.N:
+        raise ValueError(f'pred must hold B*V and x B*N values (V = {graph.V}, N = {graph.N})')
+    if out is None:
+        out = (torch.empty_like(pred), torch.empty(B, dtype=torch.int32, device=pred.device),
+               torch.empty(B, dtype=torch.int32, device=pred.device))
+    if len(out) not in (2, 3):
+        raise ValueError('out must be (ehat, status) or (ehat, status, choice)')
+    ehat, status = out[0], out[1]
+    choice = out[2] if len(out) == 3 else None
+    _require_gpu(ehat, status)
+    if (ehat.dtype != pred.dtype or ehat.numel() != pred.numel() or not ehat.is_contiguous()
+            or status.dtype != torch.int32 or status.numel() != B or not status.is_contiguous()):
+        raise ValueError(f'out must be (contiguous {pred.dtype} [{B * graph.V}], contiguous int32 [{B}], ...)')
+    if choice is not None:
+        _require_gpu(choice)
+        if choice.dtype != torch.int32 or choice.numel() != B or not choice.is_contiguous():
+            raise ValueError(f'choice must be contiguous int32 [{B}]')
+    _osd_impl(graph, x, pred, base, method, order, ehat, status, choice)
+    return ehat, status, choice
+
+
+def _osd_impl(graph, x, pred, base, method, order, ehat, status, choice):
+    """gnnd::osd / gnnd::osd_out implementation (gnndecode.library)."""
+    _lib.call('gnnd_osd', graph.handle, dtype_code(pred.dtype), _ptr(x), _ptr(pred),
+              _lib.OSD_BASE[base], _lib.OSD_METHOD[method], order, _ptr(ehat), _ptr(status),
+              None if choice is None else _ptr(choice), pred.numel() // graph.V,
+              current_stream(pred.device))
+
+
+def osd_host(H, x, pred, base='zero', method='cs', order=10):
+    """The host mirror of osd (gnnd_osd_host): numpy in, numpy out, no device.  H [V, C], x [B*N],
+    pred [B*V] float32 or float64 -> (ehat like pred, status int32 [B], choice int32 [B])."""
+    import numpy as np
+    from .graph import edge_list
+    _osd_check_method(base, method, order)
+    H = np.asarray(H)
+    V, C = H.shape
+    pred = np.ascontiguousarray(pred)
+    if pred.dtype not in (np.float32, np.float64):
+        raise TypeError(f'osd_host supports float32/float64, got {pred.dtype}')
+    x = np.ascontiguousarray(x, dtype=pred.dtype)
+    B = pred.size // V
+    if pred.size != B * V or x.size != B * (V + C):
+        raise ValueError(f'pred must hold B*V and x B*N values (V = {V}, N = {V + C})')
+    var, chk = edge_list(H)
+    ehat = np.empty_like(pred)
+    status = np.empty(B, np.int32)
+    choice = np.empty(B, np.int32)
+    P64, P32 = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
+    _lib.call('gnnd_osd_host', var.ctypes.data_as(P64), chk.ctypes.data_as(P64), var.size, V, C,
+              _lib.F32 if pred.dtype == np.float32 else _lib.F64, x.ctypes.data, pred.ctypes.data,
+              _lib.OSD_BASE[base], _lib.OSD_METHOD[method], order, ehat.ctypes.data,
+              status.ctypes.data_as(P32), choice.ctypes.data_as(P32), B)
+    return ehat, status, choice
+
+
 class SyndromeLossFn(torch.autograd.Function):
     """Batch-summed syndrome loss; backward scales the kernel's d loss / d pred."""
 

@@ -420,6 +420,45 @@ int gnnd_osd0_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges
                    int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
                    const void* h_pred, int base, void* h_ehat, int32_t* h_status, int64_t batch);
 
+/* ---- higher-order OSD: combination sweep and exhaustive reprocessing ----------------------
+ * OSD-0 returns the one solution supported on the first independent columns.  gnnd_osd starts
+ * there and picks the lightest of a fixed list of further solutions ("OSD-CS" / "OSD-E" of
+ * BP+OSD).  Target t, base z, keys, column order with its tie rule, pivot rule and failure rule
+ * are those of gnnd_osd0, unchanged.  After its Gauss-Jordan, per codeword, with (r_i, j_i) the
+ * pivot rows and columns, s the reduced residual syndrome and A the reduced matrix:
+ *   failure    gnnd_osd0 would fail (an unused row keeps s = 1): d_ehat = z, d_status = 1,
+ *              d_choice = 0; no candidate is tried.
+ *   free       f_0 .. f_{F-1}: every non-pivot column, in the column order (descending key,
+ *              ties by ascending v): the dependent columns met before rank C was reached and
+ *              every column after the walk stopped.
+ *   candidate  a set S of free columns: e[f] = 1 for f in S, e[j_i] = s[r_i] xor XOR_{f in S}
+ *              A[r_i][f], e = 0 elsewhere.  Every candidate satisfies the syndrome.  Its cost
+ *              is the Hamming weight of e: the flips relative to the base z (for
+ *              GNND_OSD_BASE_ZERO the weight of the estimate itself).  An integer: the result
+ *              is exact in both dtypes.
+ *   methods    lambda = min(order, F)
+ *              GNND_OSD_0   only the empty set; `order` is ignored (but must be >= 0): bit for
+ *                           bit gnnd_osd0.
+ *              GNND_OSD_CS  candidate 0 the empty set; 1 .. F the singles {f_0} .. {f_{F-1}}
+ *                           (all free columns, whatever the order); then the pairs {f_a, f_b},
+ *                           a < b < lambda, in lexicographic (a, b) order.  order <= 64.
+ *              GNND_OSD_E   candidate m = 0 .. 2^lambda - 1 holds f_i iff bit i of m is set.
+ *                           order <= 12.
+ *   choice     the candidate of minimum cost, ties to the lowest candidate index: d_ehat =
+ *              z xor e, d_status = 0, d_choice = that index.
+ * A negative order, one above the method's limit, or an unknown method: GNND_ERR_INVALID_ARG.
+ * dtypes, layouts and the LDS limits (GNND_ERR_UNSUPPORTED, nothing launched) as for gnnd_osd0;
+ * d_choice [B] int32 may be NULL.  One launch on `stream`, no host sync (capturable); batch 0
+ * returns GNND_OK.  gnnd_osd_host is the host mirror: same definition, same bits.             */
+typedef enum gnnd_osd_method { GNND_OSD_0 = 0, GNND_OSD_CS = 1, GNND_OSD_E = 2 } gnnd_osd_method;
+int gnnd_osd(const gnnd_graph* g, int dtype, const void* d_x, const void* d_pred, int base,
+             int method, int32_t order, void* d_ehat, int32_t* d_status, int32_t* d_choice,
+             int64_t batch, void* stream);
+int gnnd_osd_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                  int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                  const void* h_pred, int base, int method, int32_t order, void* h_ehat,
+                  int32_t* h_status, int32_t* h_choice, int64_t batch);
+
 /* Adam (torch.optim.Adam update order, amsgrad/maximize off) on one flat parameter buffer of
  * n values with its two moment buffers; *d_step is the device-resident step count (double,
  * incremented by the call), so a whole training step with the update can be captured in one
