@@ -945,97 +945,83 @@ __device__ __forceinline__ f32x2 pk_fma_hi(f32x2 u, f32x2 w, f32x2 c) {
 #ifndef GNND_MLP_ONEASM
 #define GNND_MLP_ONEASM 1
 #endif
+// GNND_MLP_SPECIALIZE 1 (default): the resident kernel's iteration loop is instantiated per
+// live-unit count (10, 9, 8) of the message MLP and selected once per kernel; 0 (compile time
+// only: same-box A/B, bisecting): only the 10-unit loop is built
+#ifndef GNND_MLP_SPECIALIZE
+#define GNND_MLP_SPECIALIZE 1
+#endif
 struct Mlp10Pair {
     f32x2 w1b[10];     // {W1_k 2^-s_k, b1_k 2^-s_k}
     f32x2 w20b;        // {W2_0 2^s_0, b2}
     f32x2 w2[5];       // {W2_{2i} 2^s, W2_{2i+1} 2^s}  (w2[0].x unused)
     // MLP of the affine input u = in_scale v + in_bias with the output scaled by out_scale,
     // folded into the weights:  W1' = W1 in_scale, b1' = W1 in_bias + b1 (one fp32 fma),
-    // W2' = W2 out_scale, b2' = b2 out_scale; vmax bounds |v| for the clamp scaling
-    // units evaluated per call: the live ones, in their original order (a unit whose
-    // pre-activation is <= 0 over the whole input range [0, vmax] adds exactly +0 to every
-    // output: dropping it changes no bit; BCH(63,45)'s trained message MLP has one).
-    // GNND_MLP_PRUNE only (A/B builds): the per-call scalar branch cost more than the unit
-    // (BCH -0.3 %, LDPC -5 %, profiles/r05/experiments/ab_r05d.txt); by default all 10 run
+    // W2' = W2 out_scale, b2' = b2 out_scale; vmax bounds |v| for the clamp scaling.
+    // Live units: a unit whose pre-activation is <= 0 at both ends of the input range
+    // [0, vmax] (fp32, the folded W1', b1' the kernel evaluates; the fma is monotone in v, so
+    // it is <= 0 in between) adds exactly +0 to every output: dropping it changes no bit.
+    // BCH(63,45)'s trained message MLP has one such unit.  load() puts the live units into the
+    // first slots in their original order and counts them (nlive, wave-uniform); eval_n<NU> runs
+    // the first NU slots.  The caller picks NU ONCE, above its iteration loop (the resident
+    // kernel's switch on nlive): a branch on nlive inside every call cost more than the unit
+    // saved (BCH -0.3 %, LDPC -5 %, profiles/r05/experiments/ab_r05d.txt).
     int nlive;
     __device__ __forceinline__ void load(const float* w, float vmax, float in_scale = 1.f,
                                          float in_bias = 0.f, float out_scale = 1.f) {
-        f32x2 u1b[10];
-        float u2[10];
-        bool live[10];
+        // live mask (bit k: unit k).  A unit's folded weights do not depend on its slot.
+        uint32_t lm = 0;
 #pragma unroll
         for (int k = 0; k < 10; ++k) {
             const float w1 = w[k] * in_scale, b1 = __builtin_fmaf(w[k], in_bias, w[10 + k]);
+            const bool live = !(b1 <= 0.f && __builtin_fmaf(vmax, w1, b1) <= 0.f);
+            lm |= (live ? 1u : 0u) << k;
+        }
+        uint32_t rem = (uint32_t)__builtin_amdgcn_readfirstlane((int)lm);
+        nlive = __builtin_popcount(rem);
+        // slot j <- unit k, or zero weights (clamp(0) * 0: exact +0 when evaluated)
+        auto fold = [&](int j, int k, bool has) {
+            const float w1 = w[k] * in_scale, b1 = __builtin_fmaf(w[k], in_bias, w[10 + k]);
             int e;
             frexpf(fabsf(w1) * vmax + fabsf(b1), &e);
-            u1b[k] = f32x2{uniform(ldexpf(w1, -e)), uniform(ldexpf(b1, -e))};
-            u2[k] = uniform(ldexpf(w[20 + k] * out_scale, e));
-#ifndef GNND_MLP_PRUNE
-            live[k] = true;
-#else
-            live[k] = !(b1 <= 0.f && __builtin_fmaf(vmax, w1, b1) <= 0.f);
-#endif
-        }
-        // compact the live units to the front (uniform selects, once per kernel); the slots
-        // past them get zero weights (clamp(0) * 0: exact +0 if ever evaluated)
-        f32x2 c1b[10];
-        float c2[10];
+            const float c2 = has ? uniform(ldexpf(w[20 + k] * out_scale, e)) : 0.f;
+            w1b[j] = has ? f32x2{uniform(ldexpf(w1, -e)), uniform(ldexpf(b1, -e))} : f32x2{0.f, 0.f};
+            if (j & 1) w2[j >> 1].y = c2; else w2[j >> 1].x = c2;
+            if (j == 0) w20b = f32x2{c2, uniform(w[30] * out_scale)};
+        };
+        if (rem == 0x3ffu) {
+            // every unit live (the usual case): slot k = unit k, all reads at constant offsets and
+            // independent of each other
 #pragma unroll
-        for (int j = 0; j < 10; ++j) { c1b[j] = f32x2{0.f, 0.f}; c2[j] = 0.f; }
-        int rank = 0;
+            for (int k = 0; k < 10; ++k) fold(k, k, true);
+        } else {
+            // slot j takes the j-th live unit (the lowest set bit of what is left of the mask), read
+            // at a wave-uniform index: a few scalar ops per slot, and no folded per-unit values
+            // held in registers for a select matrix (the kernels sit at their 128-VGPR limit);
+            // the slots past nlive get zero weights
 #pragma unroll
-        for (int k = 0; k < 10; ++k) {
-#pragma unroll
-            for (int j = 0; j < 10; ++j)
-                if (live[k] && rank == j) { c1b[j] = u1b[k]; c2[j] = u2[k]; }
-            rank += live[k] ? 1 : 0;
-        }
-        nlive = __builtin_amdgcn_readfirstlane(rank);
-#pragma unroll
-        for (int k = 0; k < 10; ++k) {
-            w1b[k] = f32x2{uniform(c1b[k].x), uniform(c1b[k].y)};
-            if (k & 1) w2[k >> 1].y = uniform(c2[k]); else w2[k >> 1].x = uniform(c2[k]);
-            if (k == 0) w20b = f32x2{uniform(c2[0]), uniform(w[30] * out_scale)};
+            for (int j = 0; j < 10; ++j) {
+                const bool has = rem != 0;
+                const int k = has ? __builtin_ctz(rem) : 0;
+                rem &= rem - 1;
+                fold(j, k, has);
+            }
         }
     }
-    // the live units (nlive, wave-uniform: the dead tail is skipped by a scalar branch; slots
-    // past nlive hold zero weights, so evaluating them would be exact too)
-    __device__ __forceinline__ f32x2 eval(f32x2 u) const {
+    // the first NU slots (NU in {10, 9, 8}; exact for nlive <= NU: the slots past nlive hold
+    // zero weights)
+    template <int NU>
+    __device__ __forceinline__ f32x2 eval_n(f32x2 u) const {
+        static_assert(NU >= 8 && NU <= 10, "Mlp10Pair::eval_n: 8, 9 or 10 units");
 #if GNND_MLP_ONEASM
         // the whole MLP as ONE asm block: hipcc's hazard recognizer assumes an op_sel dst
         // forwarding hazard between consecutive inline-asm VALU blocks and puts an s_nop 0
         // before every one that reads the previous block's result (one per unit); inside a block
         // the packed FMAs are ordinary interlocked VALU dependencies (no trans ops, no DPP, no
         // dst op_sel).  Layer 1 of unit k+1 is issued before unit k's layer-2 FMA (same
-        // accumulation order: b2, then units 0..9 — identical bits).
+        // accumulation order: b2, then units 0..NU-1 — identical bits).
         f32x2 acc, h0, h1;
-#ifdef GNND_MLP_PRUNE
-        if (nlive == 9) {
-            asm("v_pk_fma_f32 %1, %3, %4, %4 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
-                "v_pk_fma_f32 %2, %3, %5, %5 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
-                "v_pk_fma_f32 %0, %1, %14, %14 op_sel:[0,0,1] op_sel_hi:[1,0,1]\n\t"
-                "v_pk_fma_f32 %1, %3, %6, %6 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
-                "v_pk_fma_f32 %0, %2, %15, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
-                "v_pk_fma_f32 %2, %3, %7, %7 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
-                "v_pk_fma_f32 %0, %1, %16, %0 op_sel_hi:[1,0,1]\n\t"
-                "v_pk_fma_f32 %1, %3, %8, %8 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
-                "v_pk_fma_f32 %0, %2, %16, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
-                "v_pk_fma_f32 %2, %3, %9, %9 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
-                "v_pk_fma_f32 %0, %1, %17, %0 op_sel_hi:[1,0,1]\n\t"
-                "v_pk_fma_f32 %1, %3, %10, %10 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
-                "v_pk_fma_f32 %0, %2, %17, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
-                "v_pk_fma_f32 %2, %3, %11, %11 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
-                "v_pk_fma_f32 %0, %1, %18, %0 op_sel_hi:[1,0,1]\n\t"
-                "v_pk_fma_f32 %1, %3, %12, %12 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
-                "v_pk_fma_f32 %0, %2, %18, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
-                "v_pk_fma_f32 %0, %1, %19, %0 op_sel_hi:[1,0,1]"
-                : "=&v"(acc), "=&v"(h0), "=&v"(h1)
-                : "v"(u), "s"(w1b[0]), "s"(w1b[1]), "s"(w1b[2]), "s"(w1b[3]), "s"(w1b[4]),
-                  "s"(w1b[5]), "s"(w1b[6]), "s"(w1b[7]), "s"(w1b[8]), "s"(w1b[9]), "s"(w20b),
-                  "s"(w2[0]), "s"(w2[1]), "s"(w2[2]), "s"(w2[3]), "s"(w2[4]));
-            return acc;
-        }
-#endif
+        if constexpr (NU == 10) {
         asm("v_pk_fma_f32 %1, %3, %4, %4 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
             "v_pk_fma_f32 %2, %3, %5, %5 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
             "v_pk_fma_f32 %0, %1, %14, %14 op_sel:[0,0,1] op_sel_hi:[1,0,1]\n\t"
@@ -1060,6 +1046,53 @@ struct Mlp10Pair {
             : "v"(u), "s"(w1b[0]), "s"(w1b[1]), "s"(w1b[2]), "s"(w1b[3]), "s"(w1b[4]),
               "s"(w1b[5]), "s"(w1b[6]), "s"(w1b[7]), "s"(w1b[8]), "s"(w1b[9]), "s"(w20b),
               "s"(w2[0]), "s"(w2[1]), "s"(w2[2]), "s"(w2[3]), "s"(w2[4]));
+        } else if constexpr (NU == 9) {
+            // (same operand numbering: %13 = w1b[9] and the high half of %19 stay unread)
+            asm("v_pk_fma_f32 %1, %3, %4, %4 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
+                "v_pk_fma_f32 %2, %3, %5, %5 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
+                "v_pk_fma_f32 %0, %1, %14, %14 op_sel:[0,0,1] op_sel_hi:[1,0,1]\n\t"
+                "v_pk_fma_f32 %1, %3, %6, %6 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
+                "v_pk_fma_f32 %0, %2, %15, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+                "v_pk_fma_f32 %2, %3, %7, %7 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
+                "v_pk_fma_f32 %0, %1, %16, %0 op_sel_hi:[1,0,1]\n\t"
+                "v_pk_fma_f32 %1, %3, %8, %8 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
+                "v_pk_fma_f32 %0, %2, %16, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+                "v_pk_fma_f32 %2, %3, %9, %9 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
+                "v_pk_fma_f32 %0, %1, %17, %0 op_sel_hi:[1,0,1]\n\t"
+                "v_pk_fma_f32 %1, %3, %10, %10 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
+                "v_pk_fma_f32 %0, %2, %17, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+                "v_pk_fma_f32 %2, %3, %11, %11 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
+                "v_pk_fma_f32 %0, %1, %18, %0 op_sel_hi:[1,0,1]\n\t"
+                "v_pk_fma_f32 %1, %3, %12, %12 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
+                "v_pk_fma_f32 %0, %2, %18, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+                "v_pk_fma_f32 %0, %1, %19, %0 op_sel_hi:[1,0,1]"
+                : "=&v"(acc), "=&v"(h0), "=&v"(h1)
+                : "v"(u), "s"(w1b[0]), "s"(w1b[1]), "s"(w1b[2]), "s"(w1b[3]), "s"(w1b[4]),
+                  "s"(w1b[5]), "s"(w1b[6]), "s"(w1b[7]), "s"(w1b[8]), "s"(w1b[9]), "s"(w20b),
+                  "s"(w2[0]), "s"(w2[1]), "s"(w2[2]), "s"(w2[3]), "s"(w2[4]));
+        } else {
+            // (%12, %13 = w1b[8], w1b[9] and %19 = w2[4] stay unread)
+            asm("v_pk_fma_f32 %1, %3, %4, %4 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
+                "v_pk_fma_f32 %2, %3, %5, %5 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
+                "v_pk_fma_f32 %0, %1, %14, %14 op_sel:[0,0,1] op_sel_hi:[1,0,1]\n\t"
+                "v_pk_fma_f32 %1, %3, %6, %6 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
+                "v_pk_fma_f32 %0, %2, %15, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+                "v_pk_fma_f32 %2, %3, %7, %7 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
+                "v_pk_fma_f32 %0, %1, %16, %0 op_sel_hi:[1,0,1]\n\t"
+                "v_pk_fma_f32 %1, %3, %8, %8 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
+                "v_pk_fma_f32 %0, %2, %16, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+                "v_pk_fma_f32 %2, %3, %9, %9 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
+                "v_pk_fma_f32 %0, %1, %17, %0 op_sel_hi:[1,0,1]\n\t"
+                "v_pk_fma_f32 %1, %3, %10, %10 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
+                "v_pk_fma_f32 %0, %2, %17, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+                "v_pk_fma_f32 %2, %3, %11, %11 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp\n\t"
+                "v_pk_fma_f32 %0, %1, %18, %0 op_sel_hi:[1,0,1]\n\t"
+                "v_pk_fma_f32 %0, %2, %18, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]"
+                : "=&v"(acc), "=&v"(h0), "=&v"(h1)
+                : "v"(u), "s"(w1b[0]), "s"(w1b[1]), "s"(w1b[2]), "s"(w1b[3]), "s"(w1b[4]),
+                  "s"(w1b[5]), "s"(w1b[6]), "s"(w1b[7]), "s"(w1b[8]), "s"(w1b[9]), "s"(w20b),
+                  "s"(w2[0]), "s"(w2[1]), "s"(w2[2]), "s"(w2[3]), "s"(w2[4]));
+        }
         return acc;
 #else
         f32x2 h, acc;
@@ -1067,10 +1100,7 @@ struct Mlp10Pair {
             : "=v"(h) : "v"(u), "s"(w1b[0]));
         acc = pk_fma_sb(h, w20b);
 #pragma unroll
-        for (int k = 1; k < 10; ++k) {
-#ifdef GNND_MLP_PRUNE
-            if (k >= 8 && k >= nlive) break;          // (uniform) pruned dead units
-#endif
+        for (int k = 1; k < NU; ++k) {
             asm("v_pk_fma_f32 %0, %1, %2, %2 op_sel:[0,0,1] op_sel_hi:[1,0,1] clamp"
                 : "=v"(h) : "v"(u), "s"(w1b[k]));
             acc = (k & 1) ? pk_fma_hi(h, w2[k >> 1], acc) : pk_fma_lo(h, w2[k >> 1], acc);
@@ -1078,7 +1108,7 @@ struct Mlp10Pair {
         return acc;
 #endif
     }
-    __device__ __forceinline__ f32x2 operator()(f32x2 u) const { return eval(u); }
+    __device__ __forceinline__ f32x2 operator()(f32x2 u) const { return eval_n<10>(u); }
     // N edge pairs at once, unit-major: the N accumulation chains interleave, so no packed
     // FMA waits on the one just issued (same per-pair operation order: identical bits)
     template <int N>
@@ -2811,6 +2841,15 @@ decode_resident_kernel(GraphView g, const T* __restrict__ w, int nw, const TI* _
         pwl = pwl_stage((const float*)w, s_pwl, (float)(G * R), -2.f, (float)(G * R - 1), kLog2e, tid);
         __syncthreads();
     }
+    // The per-lane state set-up and the T iterations, as a force-inlined generic lambda over NU =
+    // the message-MLP units the check step evaluates (Mlp10Pair::eval_n<NU>): the fp32 GNN
+    // models instantiate it per live-unit count and pick one by a wave-uniform switch below, so
+    // the hot straight-line code carries no branch on the count.  The set-up is inside because a
+    // switch between it and the loops made the register allocator spill ~40 of its values across
+    // the switch (188 bytes of scratch per lane on the headline plan).  Every other model has the
+    // one NU = 10 body.  (The body keeps the kernel's indentation.)
+    auto run_iters = [&](auto nuc) __attribute__((always_inline)) {
+    constexpr int NU = decltype(nuc)::value;
 #pragma unroll
     for (int q = 0; q < QMAX; ++q) {
         const int f = tid + q * GNND_BLOCK;
@@ -2992,7 +3031,7 @@ decode_resident_kernel(GraphView g, const T* __restrict__ w, int nw, const TI* _
 #ifdef GNND_MLP_PWL_ONLY
                     const f32x2 y = pwl_eval2(s_pwl, pwl, u);          // (A/B: no unit fallback)
 #else
-                    const f32x2 y = pwl.ok ? pwl_eval2(s_pwl, pwl, u) : mlp2(u);
+                    const f32x2 y = pwl.ok ? pwl_eval2(s_pwl, pwl, u) : mlp2.template eval_n<NU>(u);
 #endif
                     if constexpr (MODEL == GNND_QGNNI) return __builtin_elementwise_fma(y, scp, mprev);
                     else return y + mprev;
@@ -3442,6 +3481,24 @@ decode_resident_kernel(GraphView g, const T* __restrict__ w, int nw, const TI* _
         }
         if constexpr (GNND_VAR_PRIO > 0) __builtin_amdgcn_s_setprio(0);
         __syncthreads();
+    }
+    };
+    // Plans with more than 64 item-state VGPRs only (the headline's Q = 9, R = 3).  The lighter
+    // plans (LDPC Q = 6, R = 4; toric R = 4) spend their spare registers on five cached variable
+    // entries (kLightRegs), and with three loop copies the allocator reloaded 10-18 spilled values
+    // per iteration in their variable step; they keep the one 10-unit body, which is exact for
+    // any live count (zero-weight tail).
+    constexpr bool kSpecialize = kBase2 && GNND_MLP_SPECIALIZE && QMAX * (2 * R + 2) > 64;
+    if constexpr (kSpecialize) {
+        // one wave-uniform switch per kernel (nlive: readfirstlane in Mlp10Pair::load); fewer
+        // than 8 live units run the NU = 8 body, whose zero-weight tail is exact
+        switch (mlp2.nlive) {
+            case 10: run_iters(std::integral_constant<int, 10>{}); break;
+            case 9: run_iters(std::integral_constant<int, 9>{}); break;
+            default: run_iters(std::integral_constant<int, 8>{}); break;
+        }
+    } else {
+        run_iters(std::integral_constant<int, 10>{});
     }
     if (iters == 0 && MODEL != GNND_V22)        // (V22: zero iterations, empty readout list)
         for (int f = tid; f < nb * V; f += GNND_BLOCK) {
