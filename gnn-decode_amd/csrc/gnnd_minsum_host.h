@@ -1,0 +1,121 @@
+// gnnd_minsum_host.h — host mirror of gnnd_minsum (include/gnnd.h): normalized / offset min-sum
+// BP on the flooding schedule with the syndrome-converged early stop, in plain C++.  No HIP types:
+// a plain host compiler builds it, so a stand-alone program can run it under host sanitizers
+// (tools/minsum_host_check.cpp).  Same definition as the kernel in gnnd_minsum.hip, bit for bit in
+// llr / iters / status: the check step in the first-min / second-min / arg-min form, a * m - b as
+// two roundings (build this header's translation unit with -ffp-contract=off), the variable sum
+// over E(v) in ascending edge order.
+#pragma once
+#include <stdint.h>
+#include <math.h>
+#include <cmath>
+#include <limits>
+#include <vector>
+#include "../../include/gnnd.h"
+
+// iters / alpha / beta / early_stop within the contract's limits
+inline bool gnnd_minsum_params_ok(double alpha, double beta, int32_t iters, int32_t early_stop) {
+    if (iters < 1 || (early_stop != 0 && early_stop != 1)) return false;
+    if (!(alpha > 0.0 && alpha <= 1.0)) return false;               // false for a NaN too
+    return beta >= 0.0 && beta <= std::numeric_limits<double>::max();
+}
+
+// out, llr, iters_out and status may each be null here (the checked entry requires out)
+template <typename T>
+int gnnd_minsum_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges, int V,
+                          int C, const T* x, double alpha, double beta, int iters, int early_stop,
+                          T* out, T* llr, int32_t* iters_out, int32_t* status, int64_t batch) {
+    if (num_edges > 65535 || V > 65535 || C > 65535) return GNND_ERR_UNSUPPORTED;
+    const int E = (int)num_edges;
+    std::vector<int> vptr(V + 1, 0), cptr(C + 1, 0), cedge(E), evar(E);
+    for (int e = 0; e < E; ++e) {
+        const int64_t v = h_var[e], c = h_chk[e];
+        if (v < 0 || v >= V || c < 0 || c >= C) return GNND_ERR_GRAPH;
+        if (e > 0 && (v < h_var[e - 1] || (v == h_var[e - 1] && c <= h_chk[e - 1])))
+            return GNND_ERR_GRAPH;                                   // sorted by (v, c), no duplicate
+        evar[e] = (int)v;
+        vptr[v + 1]++;
+        cptr[c + 1]++;
+    }
+    for (int c = 0; c < C; ++c)
+        if (cptr[c + 1] < 2) return GNND_ERR_UNSUPPORTED;
+    for (int v = 0; v < V; ++v) vptr[v + 1] += vptr[v];
+    for (int c = 0; c < C; ++c) cptr[c + 1] += cptr[c];
+    {
+        std::vector<int> fill(cptr.begin(), cptr.end() - 1);
+        for (int e = 0; e < E; ++e) cedge[fill[h_chk[e]]++] = e;
+    }
+    const T a = (T)alpha, bt = (T)beta;
+    const int N = V + C;
+    std::vector<T> msg(E), L(V);
+    for (int64_t b = 0; b < batch; ++b) {
+        const T* xv = x + b * N;
+        const T* xc = xv + V;
+        for (int e = 0; e < E; ++e) msg[e] = xv[evar[e]];
+        int it = 0, ok = 0;
+        while (it < iters) {
+            ++it;
+            for (int c = 0; c < C; ++c) {
+                T min1 = std::numeric_limits<T>::infinity(), min2 = min1;
+                int arg = -1, par = xc[c] < T(0);
+                for (int i = cptr[c]; i < cptr[c + 1]; ++i) {
+                    const T q = msg[cedge[i]];
+                    const T aq = std::fabs(q);
+                    par ^= (int)(q < T(0));
+                    if (aq < min1) { min2 = min1; min1 = aq; arg = cedge[i]; }
+                    else if (aq < min2) min2 = aq;
+                }
+                for (int i = cptr[c]; i < cptr[c + 1]; ++i) {
+                    const int e = cedge[i];
+                    const T q = msg[e];
+                    const T m = e == arg ? min2 : min1;
+                    const T am = a * m;
+                    const T d = am - bt;
+                    const T mag = d > T(0) ? d : T(0);
+                    msg[e] = (par ^ (int)(q < T(0))) ? -mag : mag;
+                }
+            }
+            for (int v = 0; v < V; ++v) {
+                T s = xv[v];
+                for (int e = vptr[v]; e < vptr[v + 1]; ++e) s = s + msg[e];
+                L[v] = s;
+                for (int e = vptr[v]; e < vptr[v + 1]; ++e) msg[e] = s - msg[e];
+            }
+            ok = 1;
+            for (int c = 0; c < C; ++c) {
+                int par = xc[c] < T(0);
+                for (int i = cptr[c]; i < cptr[c + 1]; ++i) par ^= (int)(L[evar[cedge[i]]] < T(0));
+                if (par) { ok = 0; break; }
+            }
+            if (early_stop && ok) break;
+        }
+        for (int v = 0; v < V; ++v) {
+            if (llr) llr[b * V + v] = L[v];
+            if (out) out[b * V + v] = T(1) / (T(1) + (T)exp((double)L[v]));
+        }
+        if (iters_out) iters_out[b] = it;
+        if (status) status[b] = ok ? 0 : 1;
+    }
+    return GNND_OK;
+}
+
+inline int gnnd_minsum_host_checked(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                                    int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                                    double alpha, double beta, int32_t iters, int32_t early_stop,
+                                    void* h_out, void* h_llr, int32_t* h_iters, int32_t* h_status,
+                                    int64_t batch) {
+    if (!h_var || !h_chk || num_edges <= 0 || num_var <= 0 || num_chk <= 0 || batch < 0)
+        return GNND_ERR_INVALID_ARG;
+    if (!gnnd_minsum_params_ok(alpha, beta, iters, early_stop)) return GNND_ERR_INVALID_ARG;
+    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
+    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    if (batch == 0) return GNND_OK;
+    if (!h_x || !h_out) return GNND_ERR_INVALID_ARG;
+    if (dtype == GNND_F32)
+        return gnnd_minsum_host_impl<float>(h_var, h_chk, num_edges, num_var, num_chk,
+                                            (const float*)h_x, alpha, beta, iters, early_stop,
+                                            (float*)h_out, (float*)h_llr, h_iters, h_status, batch);
+    return gnnd_minsum_host_impl<double>(h_var, h_chk, num_edges, num_var, num_chk,
+                                         (const double*)h_x, alpha, beta, iters, early_stop,
+                                         (double*)h_out, (double*)h_llr, h_iters, h_status, batch);
+}

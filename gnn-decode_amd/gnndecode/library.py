@@ -16,6 +16,10 @@ a custom op costs more than the 0.47 ms headline kernel, measured r02n):
   gnnd::osd0_out(graph_id, x, pred, base, ehat, status)       the same into its outputs (mutates)
   gnnd::osd(graph_id, x, pred, base, method, order) -> (ehat, status, choice)   higher-order OSD
   gnnd::osd_out(graph_id, x, pred, base, method, order, ehat, status, choice)   the same, mutating
+  gnnd::minsum(graph_id, x, iters, alpha, beta, early_stop) -> (pred, llr, iters_used, status)
+      min-sum BP with the syndrome-converged early stop
+  gnnd::minsum_out(graph_id, x, iters, alpha, beta, early_stop, pred, llr, iters_used, status)
+      the same into its outputs (mutates)
 
 The single-codeword Tanner graph is a device object owned by libgnnd, not a tensor: ops
 take the integer id that `register_graph` hands out (TannerGraph does this on creation;
@@ -211,4 +215,44 @@ def osd_out(graph_id: int, x: Tensor, pred: Tensor, base: str, method: str, orde
 
 @osd_out.register_fake
 def _osd_out_fake(graph_id, x, pred, base, method, order, ehat, status, choice):
+    return None
+
+
+# ---------------------------------------------------------------------------------------
+# min-sum BP with the syndrome-converged early stop
+# ---------------------------------------------------------------------------------------
+@torch.library.custom_op('gnnd::minsum', mutates_args=(), device_types='cuda')
+def minsum(graph_id: int, x: Tensor, iters: int, alpha: float, beta: float,
+           early_stop: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    from . import ops
+    g = graph_of(graph_id)
+    x = x.contiguous()
+    B = x.numel() // g.N
+    pred = torch.empty(B * g.V, 1, dtype=x.dtype, device=x.device)
+    llr = torch.empty(B * g.V, 1, dtype=x.dtype, device=x.device)
+    iters_used = torch.empty(B, dtype=torch.int32, device=x.device)
+    status = torch.empty(B, dtype=torch.int32, device=x.device)
+    ops._minsum_impl(g, x, iters, alpha, beta, early_stop, pred, llr, iters_used, status)
+    return pred, llr, iters_used, status
+
+
+@minsum.register_fake
+def _minsum_fake(graph_id, x, iters, alpha, beta, early_stop):
+    V, C, N, E = _DIMS[graph_id]
+    B = x.numel() // N
+    return (x.new_empty(B * V, 1), x.new_empty(B * V, 1), x.new_empty(B, dtype=torch.int32),
+            x.new_empty(B, dtype=torch.int32))
+
+
+@torch.library.custom_op('gnnd::minsum_out',
+                         mutates_args=('pred', 'llr', 'iters_used', 'status'), device_types='cuda')
+def minsum_out(graph_id: int, x: Tensor, iters: int, alpha: float, beta: float, early_stop: bool,
+               pred: Tensor, llr: Tensor, iters_used: Tensor, status: Tensor) -> None:
+    from . import ops
+    ops._minsum_impl(graph_of(graph_id), x.contiguous(), iters, alpha, beta, early_stop, pred,
+                     llr, iters_used, status)
+
+
+@minsum_out.register_fake
+def _minsum_out_fake(graph_id, x, iters, alpha, beta, early_stop, pred, llr, iters_used, status):
     return None

@@ -737,6 +737,101 @@ def osd_host(H, x, pred, base='zero', method='cs', order=10):
     return ehat, status, choice
 
 
+# ---------------------------------------------------------------------------------------
+# min-sum BP with the syndrome-converged early stop (gnnd_minsum)
+# ---------------------------------------------------------------------------------------
+def _minsum_check_params(iters, alpha, beta):
+    if not isinstance(iters, int) or isinstance(iters, bool) or not 1 <= iters <= 2 ** 31 - 1:
+        raise ValueError(f'iters must be an integer >= 1, got {iters!r}')
+    alpha, beta = float(alpha), float(beta)
+    if not 0.0 < alpha <= 1.0:
+        raise ValueError(f'alpha must be in (0, 1], got {alpha!r}')
+    if not 0.0 <= beta < float('inf'):
+        raise ValueError(f'beta must be finite and >= 0, got {beta!r}')
+    return alpha, beta
+
+
+def minsum(graph, x, iters, alpha=0.75, beta=0.0, early_stop=True, out=None):
+    """Normalized / offset min-sum BP on the flooding schedule, one HIP launch (gnnd_minsum,
+    defined in include/gnnd.h): x [B*N(,1)] the decoder input (priors at the variable rows, the
+    syndrome at the check rows as for osd0) -> (pred, llr, iters_used, status).  Check messages
+    are max(alpha * min|q| - beta, 0) with the sign product; with early_stop a codeword stops at
+    the first iteration whose hard decision satisfies its syndrome.  pred [B*V, 1] is
+    P(bit = 1) = 1 / (1 + exp(llr)), the tensor osd and decision_errors take; llr [B*V, 1] the
+    posterior LLRs of the last executed iteration; iters_used [B] int32 the iterations executed;
+    status [B] int32 0 where that hard decision satisfies the syndrome, else 1.  llr, iters_used
+    and status are bit-reproducible (the host mirror minsum_host gives the same bits).  No host
+    sync; `out` = (pred, llr, iters_used, status) tensors to write into, each but pred may be
+    None to skip it (returned as None)."""
+    alpha, beta = _minsum_check_params(iters, alpha, beta)
+    early_stop = bool(early_stop)
+    if torch.compiler.is_compiling():
+        if out is None:
+            return torch.ops.gnnd.minsum(graph.gid, x, iters, alpha, beta, early_stop)
+        if len(out) != 4 or any(o is None for o in out):
+            raise ValueError('traced minsum needs out = (pred, llr, iters_used, status)')
+        torch.ops.gnnd.minsum_out(graph.gid, x, iters, alpha, beta, early_stop, *out)
+        return out
+    _require_gpu(x)
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f'minsum supports float32/float64, got {x.dtype}')
+    x = x.contiguous()
+    B = x.numel() // graph.N
+    if x.numel() != B * graph.N:
+        raise ValueError(f'x must hold B*N values (N = {graph.N})')
+    if out is None:
+        out = (torch.empty(B * graph.V, 1, dtype=x.dtype, device=x.device),
+               torch.empty(B * graph.V, 1, dtype=x.dtype, device=x.device),
+               torch.empty(B, dtype=torch.int32, device=x.device),
+               torch.empty(B, dtype=torch.int32, device=x.device))
+    if len(out) != 4 or out[0] is None:
+        raise ValueError('out must be (pred, llr, iters_used, status); only pred is required')
+    _require_gpu(*out)
+    for t in out[:2]:
+        if t is not None and (t.dtype != x.dtype or t.numel() != B * graph.V
+                              or not t.is_contiguous()):
+            raise ValueError(f'pred / llr must be contiguous {x.dtype} [{B * graph.V}]')
+    for t in out[2:]:
+        if t is not None and (t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
+            raise ValueError(f'iters_used / status must be contiguous int32 [{B}]')
+    _minsum_impl(graph, x, iters, alpha, beta, early_stop, *out)
+    return tuple(out)
+
+
+def _minsum_impl(graph, x, iters, alpha, beta, early_stop, pred, llr, iters_used, status):
+    """gnnd::minsum / gnnd::minsum_out implementation (gnndecode.library)."""
+    _lib.call('gnnd_minsum', graph.handle, dtype_code(x.dtype), _ptr(x), alpha, beta, iters,
+              int(early_stop), _ptr(pred), _ptr(llr), _ptr(iters_used), _ptr(status),
+              x.numel() // graph.N, current_stream(x.device))
+
+
+def minsum_host(H, x, iters, alpha=0.75, beta=0.0, early_stop=True):
+    """The host mirror of minsum (gnnd_minsum_host): numpy in, numpy out, no device.  H [V, C],
+    x [B*N] float32 or float64 -> (pred, llr like x's dtype [B*V], iters_used, status int32 [B])."""
+    import numpy as np
+    from .graph import edge_list
+    alpha, beta = _minsum_check_params(iters, alpha, beta)
+    H = np.asarray(H)
+    V, C = H.shape
+    x = np.ascontiguousarray(x)
+    if x.dtype not in (np.float32, np.float64):
+        raise TypeError(f'minsum_host supports float32/float64, got {x.dtype}')
+    B = x.size // (V + C)
+    if x.size != B * (V + C):
+        raise ValueError(f'x must hold B*N values (N = {V + C})')
+    var, chk = edge_list(H)
+    pred = np.empty(B * V, x.dtype)
+    llr = np.empty(B * V, x.dtype)
+    iters_used = np.empty(B, np.int32)
+    status = np.empty(B, np.int32)
+    P64, P32 = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
+    _lib.call('gnnd_minsum_host', var.ctypes.data_as(P64), chk.ctypes.data_as(P64), var.size, V, C,
+              _lib.F32 if x.dtype == np.float32 else _lib.F64, x.ctypes.data, alpha, beta, iters,
+              int(bool(early_stop)), pred.ctypes.data, llr.ctypes.data,
+              iters_used.ctypes.data_as(P32), status.ctypes.data_as(P32), B)
+    return pred, llr, iters_used, status
+
+
 class SyndromeLossFn(torch.autograd.Function):
     """Batch-summed syndrome loss; backward scales the kernel's d loss / d pred."""
 

@@ -459,6 +459,53 @@ int gnnd_osd_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
                   const void* h_pred, int base, int method, int32_t order, void* h_ehat,
                   int32_t* h_status, int32_t* h_choice, int64_t batch);
 
+/* ---- min-sum BP with syndrome-converged early stop ----------------------------------------
+ * Normalized / offset min-sum belief propagation on the flooding schedule (the "BP" of the usual
+ * BP+OSD stacks and of hardware LDPC decoders): no transcendental in the loop, and a codeword
+ * stops as soon as its hard decision satisfies the measured syndrome.  Only add, subtract, one
+ * multiply, min, abs and compare touch the messages, and their order is fixed below, so d_llr,
+ * d_iters and d_status are bit-reproducible in `dtype` (T = float / double).  Per codeword b,
+ * edges in the single-graph order (sorted by (v, c)), E(v) / E(c) the edges at a variable / check:
+ *   prior     l_v = x[b*N + v]
+ *   target    t_c = (x[b*N + V + c] < 0)                      (the convention of gnnd_osd0)
+ *   a = (T)alpha, b = (T)beta, each rounded to T once
+ *   q_e = l_{v(e)} for every edge; then for it = 1 .. iters:
+ *     check step, every edge e at check c:
+ *       neg = t_c xor parity of #{ e' in E(c), e' != e : q_e' < 0 }
+ *       m   = min over e' in E(c), e' != e of |q_e'|
+ *       d   = round(round(a * m) - b)        two roundings in T, never a fused multiply-add
+ *       mag = d > 0 ? d : +0
+ *       r_e = neg ? -mag : mag
+ *     variable step, every variable v:
+ *       L_v = ((l_v + r_e1) + r_e2) + ...    E(v) in ascending edge order, left to right, in T
+ *       q_e = L_v - r_e for e in E(v)
+ *     h_v = (L_v < 0);  ok = (H^T h == t on every check);  if early_stop and ok: stop
+ *   `q < 0` is false for -0.0.  "Min over the others" is literal: two edges tying for the
+ *   minimum both see that minimum (the first-min / second-min / arg-min form is equivalent).
+ * Outputs: d_out[b*V + v] = 1 / (1 + exp(L_v)) = P(bit = 1), the tensor gnnd_osd and
+ * gnnd_decision_errors take (not part of the bit-exact contract: exp is the library's);
+ * d_llr[b*V + v] = L_v of the last executed iteration; d_iters[b] = iterations executed;
+ * d_status[b] = 0 if ok held after the last executed iteration, else 1 (the sense of gnnd_osd's
+ * status; with early_stop = 0 all `iters` iterations run and the status describes the last).
+ * d_x [B*N], d_out / d_llr [B*V] in dtype, d_iters / d_status [B] int32; d_llr, d_iters and
+ * d_status may each be NULL, d_out is required.  x must be finite: a codeword holding a NaN or an
+ * infinity has unspecified outputs, but does not fault and touches no other codeword's outputs.
+ * iters < 1, alpha not finite or outside (0, 1], beta not finite or < 0, early_stop not 0 / 1, or
+ * a NULL required pointer: GNND_ERR_INVALID_ARG, decided before any device call.  GNND_BF16, a
+ * graph with a check of degree < 2, or a per-codeword LDS tile ((E + 2 V) values of T) over
+ * 64 KiB: GNND_ERR_UNSUPPORTED, nothing launched.  batch 0 returns GNND_OK.  One launch on
+ * `stream`, one wave per codeword, no host sync (capturable).
+ * gnnd_minsum_host is the host mirror (plain C++, no device; the graph as the edge list
+ * gnnd_graph_create takes): the same definition, the same bits in llr / iters / status.      */
+int gnnd_minsum(const gnnd_graph* g, int dtype, const void* d_x, double alpha, double beta,
+                int32_t iters, int32_t early_stop, void* d_out, void* d_llr,
+                int32_t* d_iters, int32_t* d_status, int64_t batch, void* stream);
+int gnnd_minsum_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                     int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                     double alpha, double beta, int32_t iters, int32_t early_stop,
+                     void* h_out, void* h_llr, int32_t* h_iters, int32_t* h_status,
+                     int64_t batch);
+
 /* Adam (torch.optim.Adam update order, amsgrad/maximize off) on one flat parameter buffer of
  * n values with its two moment buffers; *d_step is the device-resident step count (double,
  * incremented by the call), so a whole training step with the update can be captured in one
