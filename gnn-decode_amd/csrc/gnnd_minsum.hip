@@ -5,6 +5,7 @@
 // device and in the host mirror alike.
 #include "gnnd_common.h"
 #include "gnnd_minsum_host.h"
+#include "gnnd_bposd_host.h"
 
 // this translation unit's debug word: gnnd_debug_take_minsum() (the collector list of
 // gnnd_debug_flags lives in the decoder's translation unit, which this feature leaves alone;
@@ -201,4 +202,48 @@ extern "C" int gnnd_minsum_host(const int64_t* h_var, const int64_t* h_chk, int6
                                 int64_t batch) {
     return gnnd_minsum_host_checked(h_var, h_chk, num_edges, num_var, num_chk, dtype, h_x, alpha,
                                     beta, iters, early_stop, h_out, h_llr, h_iters, h_status, batch);
+}
+
+// ---------------------------------------------------------------------------------------
+// gnnd_bposd: gnnd_minsum, then gnnd_osd_gated with the min-sum status as the gate.  Every refusal
+// of either stage is decided here, before the first launch.
+// ---------------------------------------------------------------------------------------
+bool gnnd_osd_fits(const gnnd_graph* g, size_t elem);      // gnnd_osd.hip: the LDS limits of gnnd_osd
+
+extern "C" int gnnd_bposd(const gnnd_graph* g, int dtype, const void* d_x, double alpha,
+                          double beta, int32_t iters, int32_t early_stop, int base, int method,
+                          int32_t order, void* d_pred, void* d_llr, int32_t* d_iters,
+                          int32_t* d_bp_status, void* d_ehat, int32_t* d_status,
+                          int32_t* d_choice, void* d_work, int64_t work_bytes, int64_t batch,
+                          void* stream) {
+    if (!g || batch < 0) return GNND_ERR_INVALID_ARG;
+    if (!gnnd_bposd_params_ok(alpha, beta, iters, early_stop, base, method, order))
+        return GNND_ERR_INVALID_ARG;
+    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
+    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    if (batch == 0) return GNND_OK;
+    if (!d_x || !d_pred || !d_llr || !d_bp_status || !d_ehat || !d_status || !d_work)
+        return GNND_ERR_INVALID_ARG;
+    if (batch > kOsdGatedMaxBatch) return GNND_ERR_UNSUPPORTED;
+    if (work_bytes < gnnd_osd_gated_bytes(batch)) return GNND_ERR_INVALID_ARG;
+    const size_t elem = dtype == GNND_F32 ? sizeof(float) : sizeof(double);
+    if (g->min_dc < 2 || minsum_plan(g->view.V, g->view.E, elem).waves == 0 ||
+        !gnnd_osd_fits(g, elem))
+        return GNND_ERR_UNSUPPORTED;
+    const int st = gnnd_minsum(g, dtype, d_x, alpha, beta, iters, early_stop, d_pred, d_llr,
+                               d_iters, d_bp_status, batch, stream);
+    if (st != GNND_OK) return st;
+    return gnnd_osd_gated(g, dtype, d_x, d_pred, d_llr, d_bp_status, base, method, order, d_ehat,
+                          d_status, d_choice, d_work, work_bytes, batch, stream);
+}
+
+extern "C" int gnnd_bposd_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                               int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                               double alpha, double beta, int32_t iters, int32_t early_stop,
+                               int base, int method, int32_t order, void* h_pred, void* h_llr,
+                               int32_t* h_iters, int32_t* h_bp_status, void* h_ehat,
+                               int32_t* h_status, int32_t* h_choice, int64_t batch) {
+    return gnnd_bposd_host_checked(h_var, h_chk, num_edges, num_var, num_chk, dtype, h_x, alpha,
+                                   beta, iters, early_stop, base, method, order, h_pred, h_llr,
+                                   h_iters, h_bp_status, h_ehat, h_status, h_choice, batch);
 }

@@ -20,11 +20,34 @@ inline bool gnnd_minsum_params_ok(double alpha, double beta, int32_t iters, int3
     return beta >= 0.0 && beta <= std::numeric_limits<double>::max();
 }
 
-// out, llr, iters_out and status may each be null here (the checked entry requires out)
+// The kernel's fp64 exponential (g_exp(double), gnnd_common.h), operation for operation: k =
+// rint(x log2 e), r = x - k ln2 with a two-part ln2, the degree-13 Taylor polynomial by Horner in
+// fused multiply-adds, ldexp.  Every step is one correctly rounded IEEE operation, so a host
+// compiler gives the device's bits.  gnnd_bposd_host computes its fp64 soft output with it: its
+// OSD stage orders the columns by that output, and the order must be the device's.
+inline double gnnd_exp_f64_device(double x) {
+    static const double coef[13] = {
+        1.0 / 6227020800.0, 1.0 / 479001600.0, 1.0 / 39916800.0, 1.0 / 3628800.0,
+        1.0 / 362880.0, 1.0 / 40320.0, 1.0 / 5040.0, 1.0 / 720.0, 1.0 / 120.0, 1.0 / 24.0,
+        1.0 / 6.0, 0.5, 1.0};
+    x = std::fmin(std::fmax(x, -750.0), 710.0);
+    const double k = std::rint(x * 1.4426950408889634);
+    double r = std::fma(-k, 6.93147180369123816490e-01, x);
+    r = std::fma(-k, 1.90821492927058770002e-10, r);
+    double p = coef[0];
+    for (int i = 1; i < 13; ++i) p = std::fma(p, r, coef[i]);
+    p = std::fma(p, r, 1.0);
+    return std::ldexp(p, (int)k);
+}
+
+// out, llr, iters_out and status may each be null here (the checked entry requires out).
+// device_exp: the fp64 soft output through gnnd_exp_f64_device instead of the host library's exp
+// (gnnd_bposd_host; gnnd_minsum_host keeps the library's)
 template <typename T>
 int gnnd_minsum_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges, int V,
                           int C, const T* x, double alpha, double beta, int iters, int early_stop,
-                          T* out, T* llr, int32_t* iters_out, int32_t* status, int64_t batch) {
+                          T* out, T* llr, int32_t* iters_out, int32_t* status, int64_t batch,
+                          bool device_exp = false) {
     if (num_edges > 65535 || V > 65535 || C > 65535) return GNND_ERR_UNSUPPORTED;
     const int E = (int)num_edges;
     std::vector<int> vptr(V + 1, 0), cptr(C + 1, 0), cedge(E), evar(E);
@@ -91,7 +114,11 @@ int gnnd_minsum_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t nu
         }
         for (int v = 0; v < V; ++v) {
             if (llr) llr[b * V + v] = L[v];
-            if (out) out[b * V + v] = T(1) / (T(1) + (T)exp((double)L[v]));
+            if (!out) continue;
+            if (device_exp && sizeof(T) == sizeof(double))
+                out[b * V + v] = T(1) / (T(1) + (T)gnnd_exp_f64_device((double)L[v]));
+            else
+                out[b * V + v] = T(1) / (T(1) + (T)exp((double)L[v]));
         }
         if (iters_out) iters_out[b] = it;
         if (status) status[b] = ok ? 0 : 1;
@@ -103,7 +130,7 @@ inline int gnnd_minsum_host_checked(const int64_t* h_var, const int64_t* h_chk, 
                                     int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
                                     double alpha, double beta, int32_t iters, int32_t early_stop,
                                     void* h_out, void* h_llr, int32_t* h_iters, int32_t* h_status,
-                                    int64_t batch) {
+                                    int64_t batch, bool device_exp = false) {
     if (!h_var || !h_chk || num_edges <= 0 || num_var <= 0 || num_chk <= 0 || batch < 0)
         return GNND_ERR_INVALID_ARG;
     if (!gnnd_minsum_params_ok(alpha, beta, iters, early_stop)) return GNND_ERR_INVALID_ARG;
@@ -114,8 +141,10 @@ inline int gnnd_minsum_host_checked(const int64_t* h_var, const int64_t* h_chk, 
     if (dtype == GNND_F32)
         return gnnd_minsum_host_impl<float>(h_var, h_chk, num_edges, num_var, num_chk,
                                             (const float*)h_x, alpha, beta, iters, early_stop,
-                                            (float*)h_out, (float*)h_llr, h_iters, h_status, batch);
+                                            (float*)h_out, (float*)h_llr, h_iters, h_status, batch,
+                                            device_exp);
     return gnnd_minsum_host_impl<double>(h_var, h_chk, num_edges, num_var, num_chk,
                                          (const double*)h_x, alpha, beta, iters, early_stop,
-                                         (double*)h_out, (double*)h_llr, h_iters, h_status, batch);
+                                         (double*)h_out, (double*)h_llr, h_iters, h_status, batch,
+                                         device_exp);
 }

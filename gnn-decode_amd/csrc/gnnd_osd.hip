@@ -1,5 +1,5 @@
-// gnnd_osd.hip — OSD post-processing (gnnd_osd0 / gnnd_osd, include/gnnd.h): turns the decoders'
-// soft outputs into an estimate that satisfies the measured syndrome whenever one exists (order
+// gnnd_osd.hip — OSD post-processing (gnnd_osd0 / gnnd_osd / gnnd_osd_gated, include/gnnd.h): turns
+// the decoders' soft outputs into an estimate that satisfies the measured syndrome whenever one exists (order
 // 0), and among the higher-order candidates (combination sweep, exhaustive) the lightest one.
 #include "gnnd_common.h"
 #include "gnnd_osd_host.h"
@@ -250,123 +250,245 @@ __device__ __forceinline__ uint32_t osd_col_mask(const uint32_t* A, int S, int C
     return m;
 }
 
+// ---- one codeword of gnnd_osd on the wave's tile: phases 1-7, then e, status and choice ----
+template <typename T>
+__device__ __forceinline__ void osd_codeword(const OsdTile<T>& t, const GraphView& g,
+                                             const OsdPlan& pl, int hard, int method, int order,
+                                             const T* __restrict__ x, const T* __restrict__ pred,
+                                             T* __restrict__ ehat, int32_t* __restrict__ status,
+                                             int32_t* __restrict__ choice, int64_t b, int lane) {
+    const int V = g.V, C = g.C, N = g.N;
+    const int S = pl.stride, syn = pl.words, rpl = pl.rpl;
+    const bool one = rpl == 1;
+    const uint32_t* A = t.A;
+    uint16_t* s_order = t.order;
+    uint8_t* s_e = t.e;
+    osd_keys_and_order(t, V, hard, pred + b * V, lane);
+    osd_build_rows(t, g, pl, x + b * N + V, lane);
+    const uint32_t used = osd_eliminate(t, pl, V, C, lane);
+    uint32_t smask = 0;                 // bit k: reduced s of row lane + 64 k
+    for (int k = 0; k < rpl; ++k) {
+        const int r = lane + 64 * k;
+        if (r < C) smask |= (A[(size_t)r * S + syn] & 1u) << k;
+    }
+    const bool fail = __ballot((smask & ~used) != 0) != 0;
+    int best_idx = 0;
+    if (!fail) {
+        uint32_t fm = smask;            // the chosen candidate's s xor its columns
+        if (method != GNND_OSD_0) {
+            // ---- free list: mark the pivot columns, compact the order in place ----
+            for (int k = 0; k < rpl; ++k)
+                if ((used >> k) & 1u)
+                    s_e[GNND_DIDX((int)t.piv[lane + 64 * k], V, GNND_DBG_VAR)] |= 2;
+            osd_wave_sync();
+            int F = 0;
+            for (int base = 0; base < V; base += 64) {
+                const int pos = base + lane;
+                int v = 0;
+                bool fr = false;
+                if (pos < V) {
+                    v = GNND_DIDX((int)s_order[pos], V, GNND_DBG_VAR);
+                    fr = !(s_e[v] & 2);
+                }
+                const unsigned long long m = __ballot(fr);
+                osd_wave_sync();        // every slot of the chunk read before one is rewritten
+                if (fr)
+                    s_order[GNND_DIDX(F + __popcll(m & ((1ull << lane) - 1)), pos + 1,
+                                      GNND_DBG_LDS_POS)] = (uint16_t)v;
+                F += __popcll(m);
+            }
+            osd_wave_sync();
+            GNND_DCHECK(F <= V, GNND_DBG_LDS_POS);
+            // ---- candidates ----
+            int best = osd_weight(smask & used, one);
+            const int lam = order < F ? order : F;
+            if (method == GNND_OSD_CS) {
+                int ba = -1, bb = -1;
+                for (int i = 0; i < F; ++i) {
+                    const int f = GNND_DIDX((int)s_order[i], V, GNND_DBG_VAR);
+                    const uint32_t m = smask ^ osd_col_mask(A, S, C, rpl, lane, f);
+                    const int c = 1 + osd_weight(m & used, one);
+                    if (c < best) { best = c; best_idx = 1 + i; ba = i; }
+                }
+                int idx = 1 + F;
+                for (int a = 0; a + 1 < lam; ++a) {
+                    const int fa = GNND_DIDX((int)s_order[a], V, GNND_DBG_VAR);
+                    const uint32_t ma = smask ^ osd_col_mask(A, S, C, rpl, lane, fa);
+                    for (int q = a + 1; q < lam; ++q, ++idx) {
+                        const int fq = GNND_DIDX((int)s_order[q], V, GNND_DBG_VAR);
+                        const uint32_t m = ma ^ osd_col_mask(A, S, C, rpl, lane, fq);
+                        const int c = 2 + osd_weight(m & used, one);
+                        if (c < best) { best = c; best_idx = idx; ba = a; bb = q; }
+                    }
+                }
+                if (ba >= 0) {
+                    const int fa = GNND_DIDX((int)s_order[ba], V, GNND_DBG_VAR);
+                    fm ^= osd_col_mask(A, S, C, rpl, lane, fa);
+                    if (lane == 0) s_e[fa] ^= 1;
+                }
+                if (bb >= 0) {
+                    const int fq = GNND_DIDX((int)s_order[bb], V, GNND_DBG_VAR);
+                    fm ^= osd_col_mask(A, S, C, rpl, lane, fq);
+                    if (lane == 0) s_e[fq] ^= 1;
+                }
+            } else {
+                uint32_t run = smask;
+                int gray = 0;           // the subset visited: Gray code of the step
+                for (int i = 1; i < (1 << lam); ++i) {
+                    const int bit = __builtin_ctz(i);
+                    gray ^= 1 << bit;
+                    const int f = GNND_DIDX((int)s_order[bit], V, GNND_DBG_VAR);
+                    run ^= osd_col_mask(A, S, C, rpl, lane, f);
+                    const int c = __popc(gray) + osd_weight(run & used, one);
+                    if (c < best || (c == best && gray < best_idx)) { best = c; best_idx = gray; }
+                }
+                for (int i = 0; i < lam; ++i)
+                    if ((best_idx >> i) & 1) {
+                        const int f = GNND_DIDX((int)s_order[i], V, GNND_DBG_VAR);
+                        fm ^= osd_col_mask(A, S, C, rpl, lane, f);
+                        if (lane == 0) s_e[f] ^= 1;
+                    }
+            }
+        }
+        // ---- solution: the pivots of the rows the chosen mask leaves set ----
+        for (int k = 0; k < rpl; ++k)
+            if ((used >> k) & (fm >> k) & 1u)
+                s_e[GNND_DIDX((int)t.piv[lane + 64 * k], V, GNND_DBG_VAR)] ^= 1;
+    }
+    osd_wave_sync();
+    T* eb = ehat + b * V;
+    for (int v = lane; v < V; v += 64) eb[v] = (s_e[v] & 1) ? T(1) : T(0);
+    if (lane == 0) {
+        status[b] = fail ? 1 : 0;
+        if (choice) choice[b] = best_idx;
+    }
+    osd_wave_sync();                    // tile reads done before the next codeword's writes
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256)
 osd_kernel(GraphView g, OsdPlan pl, int hard, int method, int order, const T* __restrict__ x,
            const T* __restrict__ pred, T* __restrict__ ehat, int32_t* __restrict__ status,
            int32_t* __restrict__ choice, int64_t B) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int V = g.V, C = g.C, N = g.N;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int S = pl.stride, syn = pl.words, rpl = pl.rpl;
-    const bool one = rpl == 1;
     const OsdTile<T> t(smem + (size_t)wave * pl.wave_bytes, pl);
-    const uint32_t* A = t.A;
-    uint16_t* s_order = t.order;
-    uint8_t* s_e = t.e;
-
     for (int64_t b = (int64_t)blockIdx.x * pl.waves + wave; b < B;
-         b += (int64_t)gridDim.x * pl.waves) {
-        osd_keys_and_order(t, V, hard, pred + b * V, lane);
-        osd_build_rows(t, g, pl, x + b * N + V, lane);
-        const uint32_t used = osd_eliminate(t, pl, V, C, lane);
-        uint32_t smask = 0;                 // bit k: reduced s of row lane + 64 k
-        for (int k = 0; k < rpl; ++k) {
-            const int r = lane + 64 * k;
-            if (r < C) smask |= (A[(size_t)r * S + syn] & 1u) << k;
+         b += (int64_t)gridDim.x * pl.waves)
+        osd_codeword(t, g, pl, hard, method, order, x, pred, ehat, status, choice, b, lane);
+}
+
+// ---------------------------------------------------------------------------------------
+// gated OSD (gnnd_osd_gated): only the codewords with gate != 0 are eliminated.  The host does not
+// know how many there are, so two launches share the caller's scratch, int32 count then int32
+// list[B]:
+//   osd_gate_kernel   workgroup 0 strides over the gate and writes the ascending list of gated
+//                     codewords and their count: per chunk of 4096 every lane owns four
+//                     consecutive codewords, one __ballot per item gives the prefix inside the
+//                     wave, the 16 wave totals cross the workgroup through LDS (two buffers: one
+//                     barrier per chunk), the running base stays in a register.  No atomics, so
+//                     no counter to clear.  The other workgroups write the pass-through outputs
+//                     of the ungated codewords, 64 codewords per workgroup step, consecutive
+//                     lanes on consecutive elements;
+//   osd_gated_kernel  osd_kernel's plan and grid (the worst case); wave w takes list entries
+//                     w, w + (waves in flight), ... below the count it reads from the scratch and
+//                     runs osd_codeword on list[i].  With count 0 every wave leaves at once.
+// ---------------------------------------------------------------------------------------
+constexpr int kGateThreads = 1024;          // 16 waves
+constexpr int kGatePerLane = 4;
+constexpr int kGateChunk = kGateThreads * kGatePerLane;
+constexpr int kGateRows = 64;               // codewords per pass-through step of a workgroup
+constexpr int64_t kGateMaxBlocks = 2048;
+
+template <typename T>
+__global__ void __launch_bounds__(kGateThreads)
+osd_gate_kernel(int V, const int32_t* __restrict__ gate, const T* __restrict__ pred,
+                const T* __restrict__ llr, T* __restrict__ ehat, int32_t* __restrict__ status,
+                int32_t* __restrict__ choice, int32_t* __restrict__ work, int64_t B) {
+    if (blockIdx.x == 0) {
+        // ---- compaction ----
+        __shared__ int s_tot[2][kGateThreads / 64];
+        int32_t* list = work + 1;
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        const unsigned long long below = (1ull << lane) - 1;
+        int base = 0;                       // gated codewords before the chunk, workgroup-uniform
+        int gv[kGatePerLane];               // the chunk's gates, loaded one chunk ahead
+#pragma unroll
+        for (int j = 0; j < kGatePerLane; ++j) {
+            const int64_t b = (int64_t)threadIdx.x * kGatePerLane + j;
+            gv[j] = b < B ? gate[b] : 0;
         }
-        const bool fail = __ballot((smask & ~used) != 0) != 0;
-        int best_idx = 0;
-        if (!fail) {
-            uint32_t fm = smask;            // the chosen candidate's s xor its columns
-            if (method != GNND_OSD_0) {
-                // ---- free list: mark the pivot columns, compact the order in place ----
-                for (int k = 0; k < rpl; ++k)
-                    if ((used >> k) & 1u)
-                        s_e[GNND_DIDX((int)t.piv[lane + 64 * k], V, GNND_DBG_VAR)] |= 2;
-                osd_wave_sync();
-                int F = 0;
-                for (int base = 0; base < V; base += 64) {
-                    const int pos = base + lane;
-                    int v = 0;
-                    bool fr = false;
-                    if (pos < V) {
-                        v = GNND_DIDX((int)s_order[pos], V, GNND_DBG_VAR);
-                        fr = !(s_e[v] & 2);
-                    }
-                    const unsigned long long m = __ballot(fr);
-                    osd_wave_sync();        // every slot of the chunk read before one is rewritten
-                    if (fr)
-                        s_order[GNND_DIDX(F + __popcll(m & ((1ull << lane) - 1)), pos + 1,
-                                          GNND_DBG_LDS_POS)] = (uint16_t)v;
-                    F += __popcll(m);
-                }
-                osd_wave_sync();
-                GNND_DCHECK(F <= V, GNND_DBG_LDS_POS);
-                // ---- candidates ----
-                int best = osd_weight(smask & used, one);
-                const int lam = order < F ? order : F;
-                if (method == GNND_OSD_CS) {
-                    int ba = -1, bb = -1;
-                    for (int i = 0; i < F; ++i) {
-                        const int f = GNND_DIDX((int)s_order[i], V, GNND_DBG_VAR);
-                        const uint32_t m = smask ^ osd_col_mask(A, S, C, rpl, lane, f);
-                        const int c = 1 + osd_weight(m & used, one);
-                        if (c < best) { best = c; best_idx = 1 + i; ba = i; }
-                    }
-                    int idx = 1 + F;
-                    for (int a = 0; a + 1 < lam; ++a) {
-                        const int fa = GNND_DIDX((int)s_order[a], V, GNND_DBG_VAR);
-                        const uint32_t ma = smask ^ osd_col_mask(A, S, C, rpl, lane, fa);
-                        for (int q = a + 1; q < lam; ++q, ++idx) {
-                            const int fq = GNND_DIDX((int)s_order[q], V, GNND_DBG_VAR);
-                            const uint32_t m = ma ^ osd_col_mask(A, S, C, rpl, lane, fq);
-                            const int c = 2 + osd_weight(m & used, one);
-                            if (c < best) { best = c; best_idx = idx; ba = a; bb = q; }
-                        }
-                    }
-                    if (ba >= 0) {
-                        const int fa = GNND_DIDX((int)s_order[ba], V, GNND_DBG_VAR);
-                        fm ^= osd_col_mask(A, S, C, rpl, lane, fa);
-                        if (lane == 0) s_e[fa] ^= 1;
-                    }
-                    if (bb >= 0) {
-                        const int fq = GNND_DIDX((int)s_order[bb], V, GNND_DBG_VAR);
-                        fm ^= osd_col_mask(A, S, C, rpl, lane, fq);
-                        if (lane == 0) s_e[fq] ^= 1;
-                    }
-                } else {
-                    uint32_t run = smask;
-                    int gray = 0;           // the subset visited: Gray code of the step
-                    for (int i = 1; i < (1 << lam); ++i) {
-                        const int bit = __builtin_ctz(i);
-                        gray ^= 1 << bit;
-                        const int f = GNND_DIDX((int)s_order[bit], V, GNND_DBG_VAR);
-                        run ^= osd_col_mask(A, S, C, rpl, lane, f);
-                        const int c = __popc(gray) + osd_weight(run & used, one);
-                        if (c < best || (c == best && gray < best_idx)) { best = c; best_idx = gray; }
-                    }
-                    for (int i = 0; i < lam; ++i)
-                        if ((best_idx >> i) & 1) {
-                            const int f = GNND_DIDX((int)s_order[i], V, GNND_DBG_VAR);
-                            fm ^= osd_col_mask(A, S, C, rpl, lane, f);
-                            if (lane == 0) s_e[f] ^= 1;
-                        }
-                }
+        int buf = 0;
+        for (int64_t c0 = 0; c0 < B; c0 += kGateChunk, buf ^= 1) {
+            const int64_t b0 = c0 + (int64_t)threadIdx.x * kGatePerLane;
+            bool f[kGatePerLane];
+#pragma unroll
+            for (int j = 0; j < kGatePerLane; ++j) f[j] = gv[j] != 0;
+#pragma unroll
+            for (int j = 0; j < kGatePerLane; ++j) {
+                const int64_t b = b0 + kGateChunk + j;
+                gv[j] = b < B ? gate[b] : 0;
             }
-            // ---- solution: the pivots of the rows the chosen mask leaves set ----
-            for (int k = 0; k < rpl; ++k)
-                if ((used >> k) & (fm >> k) & 1u)
-                    s_e[GNND_DIDX((int)t.piv[lane + 64 * k], V, GNND_DBG_VAR)] ^= 1;
+            int before = 0, wtot = 0;       // set items of the lower lanes / of the wave
+#pragma unroll
+            for (int j = 0; j < kGatePerLane; ++j) {
+                const unsigned long long m = __ballot(f[j]);
+                before += __popcll(m & below);
+                wtot += __popcll(m);
+            }
+            if (lane == 0) s_tot[buf][wave] = wtot;
+            __syncthreads();
+            int wbase = 0, tot = 0;
+            for (int w = 0; w < kGateThreads / 64; ++w) {
+                const int n = s_tot[buf][w];
+                wbase += w < wave ? n : 0;
+                tot += n;
+            }
+            int pos = base + wbase + before;
+#pragma unroll
+            for (int j = 0; j < kGatePerLane; ++j)
+                if (f[j]) list[GNND_DIDX(pos++, (int)B, GNND_DBG_GRID)] = (int32_t)(b0 + j);
+            base += tot;
         }
-        osd_wave_sync();
-        T* eb = ehat + b * V;
-        for (int v = lane; v < V; v += 64) eb[v] = (s_e[v] & 1) ? T(1) : T(0);
-        if (lane == 0) {
-            status[b] = fail ? 1 : 0;
-            if (choice) choice[b] = best_idx;
+        if (threadIdx.x == 0) work[0] = base;
+        return;
+    }
+    // ---- pass-through: the hard decision of the ungated codewords ----
+    for (int64_t g0 = (int64_t)(blockIdx.x - 1) * kGateRows; g0 < B;
+         g0 += (int64_t)(gridDim.x - 1) * kGateRows) {
+        const int rows = B - g0 < kGateRows ? (int)(B - g0) : kGateRows;
+        const unsigned n = (unsigned)rows * (unsigned)V;
+        for (unsigned i = threadIdx.x; i < n; i += kGateThreads) {
+            const unsigned r = i / (unsigned)V;
+            const int64_t b = g0 + r;
+            if (gate[b] != 0) continue;
+            const int64_t at = g0 * V + i;
+            const bool h = llr ? llr[at] < T(0) : pred[at] > T(0.5);
+            ehat[at] = h ? T(1) : T(0);
+            if (i == r * (unsigned)V) {
+                status[b] = 0;
+                if (choice) choice[b] = -1;
+            }
         }
-        osd_wave_sync();                    // tile reads done before the next codeword's writes
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+osd_gated_kernel(GraphView g, OsdPlan pl, int hard, int method, int order,
+                 const T* __restrict__ x, const T* __restrict__ pred, T* __restrict__ ehat,
+                 int32_t* __restrict__ status, int32_t* __restrict__ choice,
+                 const int32_t* __restrict__ work, int64_t B) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const OsdTile<T> t(smem + (size_t)wave * pl.wave_bytes, pl);
+    const int count = GNND_DIDX(work[0], (int)B + 1, GNND_DBG_GRID);    // <= B; the list follows
+    // count < 2^31 and at most 8192 waves in flight: the unsigned index cannot wrap; the list
+    // entry is the same for the whole wave and stays in scalar registers
+    for (unsigned i = blockIdx.x * pl.waves + wave; i < (unsigned)count; i += gridDim.x * pl.waves) {
+        const int64_t b = (unsigned)GNND_DIDX(__builtin_amdgcn_readfirstlane(work[1 + (size_t)i]),
+                                              (int)B, GNND_DBG_GRID);
+        osd_codeword(t, g, pl, hard, method, order, x, pred, ehat, status, choice, b, lane);
     }
 }
 
@@ -448,4 +570,69 @@ extern "C" int gnnd_osd_host(const int64_t* h_var, const int64_t* h_chk, int64_t
                              void* h_ehat, int32_t* h_status, int32_t* h_choice, int64_t batch) {
     return gnnd_osd_host_checked(h_var, h_chk, num_edges, num_var, num_chk, dtype, h_x, h_pred,
                                  base, method, order, h_ehat, h_status, h_choice, batch);
+}
+
+// ---- gated OSD ----
+// the LDS limits of gnnd_osd for this graph and element size (gnnd_bposd, gnnd_minsum.hip, asks
+// before its first launch)
+bool gnnd_osd_fits(const gnnd_graph* g, size_t elem) {
+    return osd_plan(g->view.V, g->view.C, elem).waves != 0;
+}
+
+template <typename T>
+static int launch_osd_gated(const gnnd_graph* g, const void* x, const void* pred, const void* llr,
+                            const int32_t* gate, int base, int method, int order, void* ehat,
+                            int32_t* status, int32_t* choice, int32_t* work, int64_t B,
+                            hipStream_t st) {
+    const GraphView& v = g->view;
+    const OsdPlan pl = osd_plan(v.V, v.C, sizeof(T));
+    if (pl.waves == 0) return GNND_ERR_UNSUPPORTED;
+    const int64_t groups = (B + kGateRows - 1) / kGateRows;
+    const unsigned blocks = 1 + (unsigned)(groups < kGateMaxBlocks ? groups : kGateMaxBlocks);
+    osd_gate_kernel<T><<<blocks, kGateThreads, 0, st>>>(v.V, gate, (const T*)pred, (const T*)llr,
+                                                        (T*)ehat, status, choice, work, B);
+    GNND_LAUNCH_CHECK();
+    osd_gated_kernel<T><<<osd_blocks(pl, B), 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
+        v, pl, base == GNND_OSD_BASE_HARD, method, order, (const T*)x, (const T*)pred, (T*)ehat,
+        status, choice, work, B);
+    GNND_LAUNCH_CHECK();
+    return GNND_OK;
+}
+
+extern "C" int gnnd_osd_gated_workspace(int64_t batch, int64_t* h_bytes) {
+    if (batch < 0 || !h_bytes) return GNND_ERR_INVALID_ARG;
+    if (batch > kOsdGatedMaxBatch) return GNND_ERR_UNSUPPORTED;
+    *h_bytes = gnnd_osd_gated_bytes(batch);
+    return GNND_OK;
+}
+
+extern "C" int gnnd_osd_gated(const gnnd_graph* g, int dtype, const void* d_x, const void* d_pred,
+                              const void* d_llr, const int32_t* d_gate, int base, int method,
+                              int32_t order, void* d_ehat, int32_t* d_status, int32_t* d_choice,
+                              void* d_work, int64_t work_bytes, int64_t batch, void* stream) {
+    if (!g || batch < 0) return GNND_ERR_INVALID_ARG;
+    if (base != GNND_OSD_BASE_ZERO && base != GNND_OSD_BASE_HARD) return GNND_ERR_INVALID_ARG;
+    if (!gnnd_osd_order_ok(method, order)) return GNND_ERR_INVALID_ARG;
+    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
+    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    if (batch == 0) return GNND_OK;
+    if (!d_x || !d_pred || !d_gate || !d_ehat || !d_status || !d_work) return GNND_ERR_INVALID_ARG;
+    if (batch > kOsdGatedMaxBatch) return GNND_ERR_UNSUPPORTED;
+    if (work_bytes < gnnd_osd_gated_bytes(batch)) return GNND_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == GNND_F32)
+        return launch_osd_gated<float>(g, d_x, d_pred, d_llr, d_gate, base, method, order, d_ehat,
+                                       d_status, d_choice, (int32_t*)d_work, batch, st);
+    return launch_osd_gated<double>(g, d_x, d_pred, d_llr, d_gate, base, method, order, d_ehat,
+                                    d_status, d_choice, (int32_t*)d_work, batch, st);
+}
+
+extern "C" int gnnd_osd_gated_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                                   int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                                   const void* h_pred, const void* h_llr, const int32_t* h_gate,
+                                   int base, int method, int32_t order, void* h_ehat,
+                                   int32_t* h_status, int32_t* h_choice, int64_t batch) {
+    return gnnd_osd_gated_host_checked(h_var, h_chk, num_edges, num_var, num_chk, dtype, h_x,
+                                       h_pred, h_llr, h_gate, base, method, order, h_ehat,
+                                       h_status, h_choice, batch);
 }

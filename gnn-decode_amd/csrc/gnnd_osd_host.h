@@ -219,3 +219,73 @@ inline int gnnd_osd_host_checked(const int64_t* h_var, const int64_t* h_chk, int
                                       (const double*)h_x, (const double*)h_pred, base, method,
                                       order, (double*)h_ehat, h_status, h_choice, batch);
 }
+
+// ---- gated OSD (gnnd_osd_gated): scratch size and host mirror ----
+// the device list of gated codewords holds int32 indices and the count check wants batch + 1
+constexpr int64_t kOsdGatedMaxBatch = 2147483646;
+// int32 count, then int32 list[batch]
+inline int64_t gnnd_osd_gated_bytes(int64_t batch) { return 4 * (batch + 1); }
+
+// The gated codewords are gathered, run through gnnd_osd_host_impl as one batch and scattered
+// back: codewords are independent, so these are the bits of the ungated call.  llr and choice may
+// be null.
+template <typename T>
+int gnnd_osd_gated_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges, int V,
+                             int C, const T* x, const T* pred, const T* llr, const int32_t* gate,
+                             int base, int method, int order, T* ehat, int32_t* status,
+                             int32_t* choice, int64_t batch) {
+    const int N = V + C;
+    std::vector<int64_t> list;
+    for (int64_t b = 0; b < batch; ++b)
+        if (gate[b] != 0) list.push_back(b);
+    const int64_t n = (int64_t)list.size();
+    std::vector<T> gx((size_t)n * N), gp((size_t)n * V), ge((size_t)n * V);
+    std::vector<int32_t> gs(n), gc(n);
+    for (int64_t i = 0; i < n; ++i) {
+        std::copy(x + list[i] * N, x + (list[i] + 1) * N, gx.begin() + i * N);
+        std::copy(pred + list[i] * V, pred + (list[i] + 1) * V, gp.begin() + i * V);
+    }
+    const int st = gnnd_osd_host_impl<T>(h_var, h_chk, num_edges, V, C, gx.data(), gp.data(), base,
+                                         method, order, ge.data(), gs.data(), gc.data(), n);
+    if (st != GNND_OK) return st;
+    for (int64_t i = 0; i < n; ++i) {
+        std::copy(ge.begin() + i * V, ge.begin() + (i + 1) * V, ehat + list[i] * V);
+        status[list[i]] = gs[i];
+        if (choice) choice[list[i]] = gc[i];
+    }
+    for (int64_t b = 0; b < batch; ++b) {
+        if (gate[b] != 0) continue;
+        for (int v = 0; v < V; ++v) {
+            const bool h = llr ? llr[b * V + v] < T(0) : pred[b * V + v] > T(0.5);
+            ehat[b * V + v] = h ? T(1) : T(0);
+        }
+        status[b] = 0;
+        if (choice) choice[b] = -1;
+    }
+    return GNND_OK;
+}
+
+inline int gnnd_osd_gated_host_checked(const int64_t* h_var, const int64_t* h_chk,
+                                       int64_t num_edges, int32_t num_var, int32_t num_chk,
+                                       int dtype, const void* h_x, const void* h_pred,
+                                       const void* h_llr, const int32_t* h_gate, int base,
+                                       int method, int32_t order, void* h_ehat, int32_t* h_status,
+                                       int32_t* h_choice, int64_t batch) {
+    if (!h_var || !h_chk || num_edges <= 0 || num_var <= 0 || num_chk <= 0 || batch < 0)
+        return GNND_ERR_INVALID_ARG;
+    if (base != GNND_OSD_BASE_ZERO && base != GNND_OSD_BASE_HARD) return GNND_ERR_INVALID_ARG;
+    if (!gnnd_osd_order_ok(method, order)) return GNND_ERR_INVALID_ARG;
+    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
+    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    if (batch == 0) return GNND_OK;
+    if (!h_x || !h_pred || !h_gate || !h_ehat || !h_status) return GNND_ERR_INVALID_ARG;
+    if (dtype == GNND_F32)
+        return gnnd_osd_gated_host_impl<float>(h_var, h_chk, num_edges, num_var, num_chk,
+                                               (const float*)h_x, (const float*)h_pred,
+                                               (const float*)h_llr, h_gate, base, method, order,
+                                               (float*)h_ehat, h_status, h_choice, batch);
+    return gnnd_osd_gated_host_impl<double>(h_var, h_chk, num_edges, num_var, num_chk,
+                                            (const double*)h_x, (const double*)h_pred,
+                                            (const double*)h_llr, h_gate, base, method, order,
+                                            (double*)h_ehat, h_status, h_choice, batch);
+}

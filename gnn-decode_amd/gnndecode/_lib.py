@@ -88,6 +88,16 @@ SIGNATURES = {
                            _vp, _vp, _i64, _vp]),
     'gnnd_minsum_host': (_int, [_c_i64p, _c_i64p, _i64, _i32, _i32, _int, _vp, ctypes.c_double,
                                 ctypes.c_double, _i32, _i32, _vp, _vp, _c_i32p, _c_i32p, _i64]),
+    'gnnd_osd_gated_workspace': (_int, [_i64, _c_i64p]),
+    'gnnd_osd_gated': (_int, [_vp, _int, _vp, _vp, _vp, _vp, _int, _int, _i32, _vp, _vp, _vp, _vp,
+                              _i64, _i64, _vp]),
+    'gnnd_osd_gated_host': (_int, [_c_i64p, _c_i64p, _i64, _i32, _i32, _int, _vp, _vp, _vp, _c_i32p,
+                                   _int, _int, _i32, _vp, _c_i32p, _c_i32p, _i64]),
+    'gnnd_bposd': (_int, [_vp, _int, _vp, ctypes.c_double, ctypes.c_double, _i32, _i32, _int, _int,
+                          _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
+    'gnnd_bposd_host': (_int, [_c_i64p, _c_i64p, _i64, _i32, _i32, _int, _vp, ctypes.c_double,
+                               ctypes.c_double, _i32, _i32, _int, _int, _i32, _vp, _vp, _c_i32p,
+                               _c_i32p, _vp, _c_i32p, _c_i32p, _i64]),
     'gnnd_v24_check_mlp_table': (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     'gnnd_adam_step': (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double,
                               ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp]),

@@ -20,6 +20,13 @@ a custom op costs more than the 0.47 ms headline kernel, measured r02n):
       min-sum BP with the syndrome-converged early stop
   gnnd::minsum_out(graph_id, x, iters, alpha, beta, early_stop, pred, llr, iters_used, status)
       the same into its outputs (mutates)
+  gnnd::osd_gated(graph_id, x, pred, gate, base, method, order, llr?) -> (ehat, status, choice)
+      osd on the codewords with gate != 0, the hard decision passed through elsewhere
+  gnnd::osd_gated_out(graph_id, x, pred, gate, base, method, order, llr?, ehat, status, choice)
+  gnnd::bposd(graph_id, x, iters, alpha, beta, early_stop, base, method, order)
+      -> (ehat, status, choice, iters_used, bp_status, pred, llr)   minsum, then osd_gated
+  gnnd::bposd_out(graph_id, x, iters, alpha, beta, early_stop, base, method, order, ehat, status,
+      choice, iters_used, bp_status, pred, llr)                     the same, mutating
 
 The single-codeword Tanner graph is a device object owned by libgnnd, not a tensor: ops
 take the integer id that `register_graph` hands out (TannerGraph does this on creation;
@@ -255,4 +262,90 @@ def minsum_out(graph_id: int, x: Tensor, iters: int, alpha: float, beta: float, 
 
 @minsum_out.register_fake
 def _minsum_out_fake(graph_id, x, iters, alpha, beta, early_stop, pred, llr, iters_used, status):
+    return None
+
+
+# ---------------------------------------------------------------------------------------
+# gated OSD and the one-call BP+OSD decoder
+# ---------------------------------------------------------------------------------------
+@torch.library.custom_op('gnnd::osd_gated', mutates_args=(), device_types='cuda')
+def osd_gated(graph_id: int, x: Tensor, pred: Tensor, gate: Tensor, base: str, method: str,
+              order: int, llr: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
+    from . import ops
+    g = graph_of(graph_id)
+    pred = pred.contiguous()
+    B = pred.numel() // g.V
+    ehat = torch.empty_like(pred)
+    status = torch.empty(B, dtype=torch.int32, device=pred.device)
+    choice = torch.empty(B, dtype=torch.int32, device=pred.device)
+    ops._osd_gated_impl(g, x.contiguous(), pred, gate.contiguous(), base, method, order,
+                        None if llr is None else llr.contiguous(), ehat, status, choice)
+    return ehat, status, choice
+
+
+@osd_gated.register_fake
+def _osd_gated_fake(graph_id, x, pred, gate, base, method, order, llr):
+    V = _DIMS[graph_id][0]
+    B = pred.numel() // V
+    return (torch.empty_like(pred, memory_format=torch.contiguous_format),
+            pred.new_empty(B, dtype=torch.int32), pred.new_empty(B, dtype=torch.int32))
+
+
+@torch.library.custom_op('gnnd::osd_gated_out', mutates_args=('ehat', 'status', 'choice'),
+                         device_types='cuda')
+def osd_gated_out(graph_id: int, x: Tensor, pred: Tensor, gate: Tensor, base: str, method: str,
+                  order: int, llr: Optional[Tensor], ehat: Tensor, status: Tensor,
+                  choice: Tensor) -> None:
+    from . import ops
+    ops._osd_gated_impl(graph_of(graph_id), x.contiguous(), pred.contiguous(), gate.contiguous(),
+                        base, method, order, None if llr is None else llr.contiguous(), ehat,
+                        status, choice)
+
+
+@osd_gated_out.register_fake
+def _osd_gated_out_fake(graph_id, x, pred, gate, base, method, order, llr, ehat, status, choice):
+    return None
+
+
+@torch.library.custom_op('gnnd::bposd', mutates_args=(), device_types='cuda')
+def bposd(graph_id: int, x: Tensor, iters: int, alpha: float, beta: float, early_stop: bool,
+          base: str, method: str, order: int
+          ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from . import ops
+    g = graph_of(graph_id)
+    x = x.contiguous()
+    B = x.numel() // g.N
+    ehat, pred, llr = (torch.empty(B * g.V, 1, dtype=x.dtype, device=x.device) for _ in range(3))
+    status, choice, iters_used, bp_status = (torch.empty(B, dtype=torch.int32, device=x.device)
+                                             for _ in range(4))
+    ops._bposd_impl(g, x, iters, alpha, beta, early_stop, base, method, order, ehat, status, choice,
+                    iters_used, bp_status, pred, llr)
+    return ehat, status, choice, iters_used, bp_status, pred, llr
+
+
+@bposd.register_fake
+def _bposd_fake(graph_id, x, iters, alpha, beta, early_stop, base, method, order):
+    V, C, N, E = _DIMS[graph_id]
+    B = x.numel() // N
+
+    def ints():
+        return x.new_empty(B, dtype=torch.int32)
+    return (x.new_empty(B * V, 1), ints(), ints(), ints(), ints(), x.new_empty(B * V, 1),
+            x.new_empty(B * V, 1))
+
+
+@torch.library.custom_op('gnnd::bposd_out',
+                         mutates_args=('ehat', 'status', 'choice', 'iters_used', 'bp_status',
+                                       'pred', 'llr'), device_types='cuda')
+def bposd_out(graph_id: int, x: Tensor, iters: int, alpha: float, beta: float, early_stop: bool,
+              base: str, method: str, order: int, ehat: Tensor, status: Tensor, choice: Tensor,
+              iters_used: Tensor, bp_status: Tensor, pred: Tensor, llr: Tensor) -> None:
+    from . import ops
+    ops._bposd_impl(graph_of(graph_id), x.contiguous(), iters, alpha, beta, early_stop, base, method,
+                    order, ehat, status, choice, iters_used, bp_status, pred, llr)
+
+
+@bposd_out.register_fake
+def _bposd_out_fake(graph_id, x, iters, alpha, beta, early_stop, base, method, order, ehat, status,
+                    choice, iters_used, bp_status, pred, llr):
     return None

@@ -832,6 +832,227 @@ def minsum_host(H, x, iters, alpha=0.75, beta=0.0, early_stop=True):
     return pred, llr, iters_used, status
 
 
+# ---------------------------------------------------------------------------------------
+# gated OSD (gnnd_osd_gated) and the one-call BP+OSD decoder (gnnd_bposd)
+# ---------------------------------------------------------------------------------------
+def osd_gated_workspace(B):
+    """Bytes of scratch gnnd_osd_gated / gnnd_bposd need for a batch of B codewords."""
+    n = ctypes.c_int64()
+    _lib.call('gnnd_osd_gated_workspace', B, ctypes.byref(n))
+    return n.value
+
+
+def _gated_work(work, B, device):
+    need = osd_gated_workspace(B)
+    if work is None:
+        return torch.empty(need, dtype=torch.uint8, device=device), need
+    _require_gpu(work)
+    have = work.numel() * work.element_size()
+    if have < need or not work.is_contiguous() or work.data_ptr() % 4:
+        raise ValueError(f'work must be a contiguous 4-byte aligned tensor of >= {need} bytes')
+    return work, have
+
+
+def _check_ehat_status_choice(out, dtype, B, V):
+    """(ehat, status[, choice]) of the OSD calls -> (ehat, status, choice or None)."""
+    if len(out) not in (2, 3):
+        raise ValueError('out must be (ehat, status) or (ehat, status, choice)')
+    ehat, status = out[0], out[1]
+    choice = out[2] if len(out) == 3 else None
+    _require_gpu(ehat, status, choice)
+    if (ehat.dtype != dtype or ehat.numel() != B * V or not ehat.is_contiguous()
+            or status.dtype != torch.int32 or status.numel() != B or not status.is_contiguous()):
+        raise ValueError(f'out must be (contiguous {dtype} [{B * V}], contiguous int32 [{B}], ...)')
+    if choice is not None and (choice.dtype != torch.int32 or choice.numel() != B
+                               or not choice.is_contiguous()):
+        raise ValueError(f'choice must be contiguous int32 [{B}]')
+    return ehat, status, choice
+
+
+def osd_gated(graph, x, pred, gate, base='zero', method='cs', order=10, llr=None, out=None,
+              work=None):
+    """osd on the codewords a gate selects (gnnd_osd_gated): gate [B] int32, for instance minsum's
+    status.  Where gate != 0, ehat / status / choice are bit for bit osd's; where gate == 0 the
+    codeword passes through: ehat is the hard decision (llr < 0 if llr [B*V(,1)] is given, else
+    pred > 0.5) as 0.0 / 1.0, status 0, choice -1, its syndrome not re-checked.  Give llr with a
+    min-sum gate: pred rounds to exactly 0.5 for a tiny |llr| and then loses the decision the
+    status was computed from.  Two launches (a compaction of the gate on the device, then osd's
+    kernel over the gated list), no host sync.  -> (ehat, status, choice); `out` as for osd;
+    `work`: a scratch tensor of osd_gated_workspace(B) bytes, allocated with torch.empty when
+    None."""
+    _osd_check_method(base, method, order)
+    if torch.compiler.is_compiling():
+        if out is None:
+            return torch.ops.gnnd.osd_gated(graph.gid, x, pred, gate, base, method, order, llr)
+        if len(out) != 3 or out[2] is None:
+            raise ValueError('traced osd_gated needs out = (ehat, status, choice)')
+        torch.ops.gnnd.osd_gated_out(graph.gid, x, pred, gate, base, method, order, llr, *out)
+        return out
+    _require_gpu(x, pred, gate, llr)
+    if x.dtype != pred.dtype or (llr is not None and llr.dtype != pred.dtype):
+        raise TypeError(f'x ({x.dtype}), pred ({pred.dtype}) and llr must share a dtype')
+    if pred.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f'osd_gated supports float32/float64, got {pred.dtype}')
+    if gate.dtype != torch.int32:
+        raise TypeError(f'gate must be int32, got {gate.dtype}')
+    x = x.contiguous()
+    pred = pred.contiguous()
+    gate = gate.contiguous()
+    B = pred.numel() // graph.V
+    if pred.numel() != B * graph.V or x.numel() != B * graph.N or gate.numel() != B:
+        raise ValueError(f'pred must hold B*V, x B*N and gate B values (V = {graph.V}, '
+                         f'N = {graph.N})')
+    if llr is not None:
+        llr = llr.contiguous()
+        if llr.numel() != pred.numel():
+            raise ValueError('llr must hold B*V values')
+    if out is None:
+        out = (torch.empty_like(pred), torch.empty(B, dtype=torch.int32, device=pred.device),
+               torch.empty(B, dtype=torch.int32, device=pred.device))
+    ehat, status, choice = _check_ehat_status_choice(out, pred.dtype, B, graph.V)
+    _osd_gated_impl(graph, x, pred, gate, base, method, order, llr, ehat, status, choice, work)
+    return ehat, status, choice
+
+
+def _osd_gated_impl(graph, x, pred, gate, base, method, order, llr, ehat, status, choice,
+                    work=None):
+    """gnnd::osd_gated / gnnd::osd_gated_out implementation (gnndecode.library)."""
+    B = pred.numel() // graph.V
+    work, nbytes = _gated_work(work, B, pred.device)
+    _lib.call('gnnd_osd_gated', graph.handle, dtype_code(pred.dtype), _ptr(x), _ptr(pred),
+              _ptr(llr), _ptr(gate), _lib.OSD_BASE[base], _lib.OSD_METHOD[method], order,
+              _ptr(ehat), _ptr(status), _ptr(choice), _ptr(work), nbytes, B,
+              current_stream(pred.device))
+
+
+def bposd(graph, x, iters, alpha=0.75, beta=0.0, early_stop=True, base='zero', method='cs',
+          order=10, out=None, work=None):
+    """The BP+OSD decoder in one call (gnnd_bposd): minsum, then osd_gated with the min-sum status
+    as the gate and the min-sum llr as the pass-through decision, three launches on the current
+    stream, no host sync.  -> (ehat, status, choice, iters_used, bp_status, pred, llr): where
+    bp_status is 0 ehat is min-sum's hard decision, which satisfies the syndrome, and choice is
+    -1; elsewhere ehat / status / choice are osd's.  Everything but pred is bit-reproducible
+    (bposd_host gives the same bits).  `out`: the seven tensors to write into, choice and
+    iters_used may be None to skip them; `work` as for osd_gated."""
+    alpha, beta = _minsum_check_params(iters, alpha, beta)
+    early_stop = bool(early_stop)
+    _osd_check_method(base, method, order)
+    if torch.compiler.is_compiling():
+        if out is None:
+            return torch.ops.gnnd.bposd(graph.gid, x, iters, alpha, beta, early_stop, base, method,
+                                        order)
+        if len(out) != 7 or any(o is None for o in out):
+            raise ValueError('traced bposd needs all seven out tensors')
+        torch.ops.gnnd.bposd_out(graph.gid, x, iters, alpha, beta, early_stop, base, method, order,
+                                 *out)
+        return out
+    _require_gpu(x)
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f'bposd supports float32/float64, got {x.dtype}')
+    x = x.contiguous()
+    B = x.numel() // graph.N
+    if x.numel() != B * graph.N:
+        raise ValueError(f'x must hold B*N values (N = {graph.N})')
+    if out is None:
+        def real():
+            return torch.empty(B * graph.V, 1, dtype=x.dtype, device=x.device)
+
+        def ints():
+            return torch.empty(B, dtype=torch.int32, device=x.device)
+        out = (real(), ints(), ints(), ints(), ints(), real(), real())
+    if len(out) != 7:
+        raise ValueError('out must be (ehat, status, choice, iters_used, bp_status, pred, llr)')
+    ehat, status, choice, iters_used, bp_status, pred, llr = out
+    if any(t is None for t in (ehat, status, bp_status, pred, llr)):
+        raise ValueError('only choice and iters_used may be None in out')
+    _require_gpu(*out)
+    for t in (ehat, pred, llr):
+        if t.dtype != x.dtype or t.numel() != B * graph.V or not t.is_contiguous():
+            raise ValueError(f'ehat / pred / llr must be contiguous {x.dtype} [{B * graph.V}]')
+    for t in (status, choice, iters_used, bp_status):
+        if t is not None and (t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
+            raise ValueError(f'status / choice / iters_used / bp_status must be contiguous int32 [{B}]')
+    _bposd_impl(graph, x, iters, alpha, beta, early_stop, base, method, order, ehat, status, choice,
+                iters_used, bp_status, pred, llr, work)
+    return tuple(out)
+
+
+def _bposd_impl(graph, x, iters, alpha, beta, early_stop, base, method, order, ehat, status, choice,
+                iters_used, bp_status, pred, llr, work=None):
+    """gnnd::bposd / gnnd::bposd_out implementation (gnndecode.library)."""
+    B = x.numel() // graph.N
+    work, nbytes = _gated_work(work, B, x.device)
+    _lib.call('gnnd_bposd', graph.handle, dtype_code(x.dtype), _ptr(x), alpha, beta, iters,
+              int(early_stop), _lib.OSD_BASE[base], _lib.OSD_METHOD[method], order, _ptr(pred),
+              _ptr(llr), _ptr(iters_used), _ptr(bp_status), _ptr(ehat), _ptr(status), _ptr(choice),
+              _ptr(work), nbytes, B, current_stream(x.device))
+
+
+def _host_graph(H):
+    import numpy as np
+    from .graph import edge_list
+    H = np.asarray(H)
+    var, chk = edge_list(H)
+    P64 = ctypes.POINTER(ctypes.c_int64)
+    return H.shape[0], H.shape[1], var, chk, var.ctypes.data_as(P64), chk.ctypes.data_as(P64)
+
+
+def osd_gated_host(H, x, pred, gate, base='zero', method='cs', order=10, llr=None):
+    """The host mirror of osd_gated (gnnd_osd_gated_host): numpy in, numpy out, no device.
+    -> (ehat like pred, status int32 [B], choice int32 [B])."""
+    import numpy as np
+    _osd_check_method(base, method, order)
+    V, C, var, chk, vp, cp = _host_graph(H)
+    pred = np.ascontiguousarray(pred)
+    if pred.dtype not in (np.float32, np.float64):
+        raise TypeError(f'osd_gated_host supports float32/float64, got {pred.dtype}')
+    x = np.ascontiguousarray(x, dtype=pred.dtype)
+    gate = np.ascontiguousarray(gate, dtype=np.int32)
+    B = pred.size // V
+    if pred.size != B * V or x.size != B * (V + C) or gate.size != B:
+        raise ValueError(f'pred must hold B*V, x B*N and gate B values (V = {V}, N = {V + C})')
+    if llr is not None:
+        llr = np.ascontiguousarray(llr, dtype=pred.dtype)
+        if llr.size != pred.size:
+            raise ValueError('llr must hold B*V values')
+    ehat = np.empty_like(pred)
+    status = np.empty(B, np.int32)
+    choice = np.empty(B, np.int32)
+    P32 = ctypes.POINTER(ctypes.c_int32)
+    _lib.call('gnnd_osd_gated_host', vp, cp, var.size, V, C,
+              _lib.F32 if pred.dtype == np.float32 else _lib.F64, x.ctypes.data, pred.ctypes.data,
+              None if llr is None else llr.ctypes.data, gate.ctypes.data_as(P32),
+              _lib.OSD_BASE[base], _lib.OSD_METHOD[method], order, ehat.ctypes.data,
+              status.ctypes.data_as(P32), choice.ctypes.data_as(P32), B)
+    return ehat, status, choice
+
+
+def bposd_host(H, x, iters, alpha=0.75, beta=0.0, early_stop=True, base='zero', method='cs',
+               order=10):
+    """The host mirror of bposd (gnnd_bposd_host): numpy in, numpy out, no device.  -> (ehat,
+    status, choice, iters_used, bp_status, pred, llr)."""
+    import numpy as np
+    alpha, beta = _minsum_check_params(iters, alpha, beta)
+    _osd_check_method(base, method, order)
+    V, C, var, chk, vp, cp = _host_graph(H)
+    x = np.ascontiguousarray(x)
+    if x.dtype not in (np.float32, np.float64):
+        raise TypeError(f'bposd_host supports float32/float64, got {x.dtype}')
+    B = x.size // (V + C)
+    if x.size != B * (V + C):
+        raise ValueError(f'x must hold B*N values (N = {V + C})')
+    ehat, pred, llr = (np.empty(B * V, x.dtype) for _ in range(3))
+    status, choice, iters_used, bp_status = (np.empty(B, np.int32) for _ in range(4))
+    P32 = ctypes.POINTER(ctypes.c_int32)
+    _lib.call('gnnd_bposd_host', vp, cp, var.size, V, C,
+              _lib.F32 if x.dtype == np.float32 else _lib.F64, x.ctypes.data, alpha, beta, iters,
+              int(bool(early_stop)), _lib.OSD_BASE[base], _lib.OSD_METHOD[method], order,
+              pred.ctypes.data, llr.ctypes.data, iters_used.ctypes.data_as(P32),
+              bp_status.ctypes.data_as(P32), ehat.ctypes.data, status.ctypes.data_as(P32),
+              choice.ctypes.data_as(P32), B)
+    return ehat, status, choice, iters_used, bp_status, pred, llr
+
+
 class SyndromeLossFn(torch.autograd.Function):
     """Batch-summed syndrome loss; backward scales the kernel's d loss / d pred."""
 

@@ -506,6 +506,78 @@ int gnnd_minsum_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edg
                      void* h_out, void* h_llr, int32_t* h_iters, int32_t* h_status,
                      int64_t batch);
 
+/* ---- gated OSD and the one-call BP+OSD decoder ---------------------------------------------
+ * gnnd_osd_gated is gnnd_osd on the codewords the caller's gate selects, the way every BP+OSD
+ * decoder joins its two stages: a codeword whose BP hard decision already satisfies its syndrome
+ * keeps that decision, only the others are reprocessed.  Per codeword b:
+ *   d_gate[b] != 0  d_ehat, d_status and d_choice of b are bit for bit what gnnd_osd writes for
+ *                   that codeword with the same base, method and order.  Codewords are
+ *                   independent: the result does not depend on which others are gated.
+ *   d_gate[b] == 0  pass-through: d_ehat[b*V + v] = h_v as exactly 0.0 / 1.0, d_status[b] = 0,
+ *                   d_choice[b] = -1, with the hard decision
+ *                     h_v = (d_llr[b*V + v] < 0)     if d_llr is not NULL (min-sum's own hard
+ *                                                    decision: false for -0.0 and for a NaN)
+ *                     h_v = (d_pred[b*V + v] > 0.5)  if d_llr is NULL (a NaN gives 0)
+ *                   The syndrome of a pass-through codeword is not re-checked: the gate is the
+ *                   caller's claim.  d_llr exists because pred = 1 / (1 + exp(L)) rounds to
+ *                   exactly 0.5 for a tiny |L|, and (pred > 0.5) then loses a decision that
+ *                   min-sum's status was computed from.
+ * d_gate [B] int32 (gnnd_minsum's d_status is one); d_llr [B*V] in dtype or NULL; the other
+ * arrays as for gnnd_osd, d_choice may be NULL.  d_work is the caller's scratch of at least
+ * gnnd_osd_gated_workspace(batch) bytes (4 * (batch + 1): an int32 count and the int32 list of
+ * gated codewords), 4-byte aligned, contents unspecified before and after; the library allocates
+ * nothing.  Two launches on `stream`: a compaction that writes the ascending list of gated
+ * codewords and the pass-through outputs, then gnnd_osd's kernel plan over that list, its length
+ * read on the device.  No host read of the gate and no synchronisation (capturable; a replay
+ * follows the gate it finds).
+ * base, method, order and dtype are checked as in gnnd_osd; a NULL required pointer or work_bytes
+ * below the workspace size: GNND_ERR_INVALID_ARG, decided before any device call.  The LDS and C
+ * limits of gnnd_osd, or batch > 2^31 - 2: GNND_ERR_UNSUPPORTED, nothing launched.  batch 0
+ * returns GNND_OK.  gnnd_osd_gated_host is the host mirror: same definition, same bits.
+ *
+ * gnnd_bposd is gnnd_minsum(d_x, alpha, beta, iters, early_stop -> d_pred, d_llr, d_iters,
+ * d_bp_status) followed by gnnd_osd_gated(d_x, d_pred, d_llr, gate = d_bp_status, base, method,
+ * order -> d_ehat, d_status, d_choice) on the same stream: three launches, no host sync.  d_pred,
+ * d_llr and d_bp_status are required (they feed the second stage); d_iters and d_choice may be
+ * NULL.  The outputs inherit the two contracts: d_llr, d_iters and d_bp_status are
+ * bit-reproducible (gnnd_minsum), and d_ehat, d_status and d_choice are gnnd_osd_gated's
+ * bit-exact function of d_x, d_pred, d_llr and the gate.  d_pred is gnnd_minsum's soft output.
+ * In GNND_F64 its exponential is a fixed sequence of correctly rounded operations (k = rint(L
+ * log2 e), r = L - k ln2 with a two-part ln2, a degree-13 Taylor polynomial by Horner in fused
+ * multiply-adds, ldexp), which gnnd_bposd_host repeats: there d_pred, and with it d_ehat,
+ * d_status and d_choice, are the same bits on the device and in the host mirror.  In GNND_F32 the
+ * device uses its math library's expf: d_pred may differ from the mirror's in the last place, and
+ * a codeword in which that changes the order of two nearly equal columns may get another
+ * (equally valid) estimate; pass-through codewords agree bit for bit in both dtypes.
+ * Guarantee: where d_bp_status[b] == 0, d_ehat of b is min-sum's own
+ * hard decision (d_llr < 0) and satisfies the syndrome exactly; elsewhere it is gnnd_osd's
+ * estimate, which satisfies it wherever d_status[b] == 0.
+ * Every GNND_ERR_INVALID_ARG of either stage is decided before the first device call;
+ * GNND_ERR_UNSUPPORTED is the union of both stages' conditions, with nothing launched; batch 0
+ * returns GNND_OK.  gnnd_bposd_host is the host mirror (gnnd_minsum_host's loop with that fp64
+ * exponential for the soft output, then gnnd_osd_gated_host).                                  */
+int gnnd_osd_gated_workspace(int64_t batch, int64_t* h_bytes);
+int gnnd_osd_gated(const gnnd_graph* g, int dtype, const void* d_x, const void* d_pred,
+                   const void* d_llr, const int32_t* d_gate, int base, int method, int32_t order,
+                   void* d_ehat, int32_t* d_status, int32_t* d_choice, void* d_work,
+                   int64_t work_bytes, int64_t batch, void* stream);
+int gnnd_osd_gated_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                        int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                        const void* h_pred, const void* h_llr, const int32_t* h_gate, int base,
+                        int method, int32_t order, void* h_ehat, int32_t* h_status,
+                        int32_t* h_choice, int64_t batch);
+int gnnd_bposd(const gnnd_graph* g, int dtype, const void* d_x, double alpha, double beta,
+               int32_t iters, int32_t early_stop, int base, int method, int32_t order,
+               void* d_pred, void* d_llr, int32_t* d_iters, int32_t* d_bp_status, void* d_ehat,
+               int32_t* d_status, int32_t* d_choice, void* d_work, int64_t work_bytes,
+               int64_t batch, void* stream);
+int gnnd_bposd_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                    int32_t num_var, int32_t num_chk, int dtype, const void* h_x, double alpha,
+                    double beta, int32_t iters, int32_t early_stop, int base, int method,
+                    int32_t order, void* h_pred, void* h_llr, int32_t* h_iters,
+                    int32_t* h_bp_status, void* h_ehat, int32_t* h_status, int32_t* h_choice,
+                    int64_t batch);
+
 /* Adam (torch.optim.Adam update order, amsgrad/maximize off) on one flat parameter buffer of
  * n values with its two moment buffers; *d_step is the device-resident step count (double,
  * incremented by the call), so a whole training step with the update can be captured in one
