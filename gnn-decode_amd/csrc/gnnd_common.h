@@ -186,6 +186,13 @@ struct gnnd_graph {
     GraphView* dcomp;
     int nosplit;              // gnnd_graph_set_split(g, 0): decode / train the graph whole
     int min_dc;               // smallest check degree (the fp32 BP ratio-form check step needs 2)
+    // Layered schedule of gnnd_minsum_layered (include/gnnd.h): the greedy layers of the checks.
+    // Kept here and not in GraphView, which every kernel takes by value.  layer_dev is one device
+    // allocation {layer_ptr[nlayers + 1], layer_chk[C]}: the checks of layer k are
+    // layer_chk[layer_ptr[k] .. layer_ptr[k + 1]), ascending; layer_of is the host's [C] copy.
+    int nlayers, max_layer;   // number of layers, checks in the largest
+    int* layer_dev;
+    int* layer_of;
 };
 constexpr int kMaxComp = 8;
 

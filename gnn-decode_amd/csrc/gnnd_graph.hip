@@ -6,6 +6,7 @@
 // (quantum/decoder_v2_4.py:164-165: H.to_sparse()._indices(), sorted by (v, c)) and the
 // kernels derive batched node/edge ids in closed form.
 #include "gnnd_common.h"
+#include "gnnd_minsum_layered_host.h"   // the layer rule (gnnd_layers_build), shared with the mirror
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -693,6 +694,33 @@ int create_single(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
             lv.ts = x ? L.ts : V;
         }
     }
+    // layered schedule (gnnd_minsum_layered): the greedy layers, kept beside the views
+    {
+        const int* cptr = table.data() + E + V + 1;
+        const int* cedge = cptr + C + 1;
+        std::vector<int> cvar(E), layer_of, layer_tab, layer_chk;
+        for (int i = 0; i < E; ++i) cvar[i] = (int)((uint32_t)table[cedge[i]] & 0xffffu);
+        g->nlayers = gnnd_layers_build(V, C, cptr, cvar.data(), layer_of);
+        gnnd_layers_order(C, g->nlayers, layer_of, layer_tab, layer_chk);
+        for (int k = 0; k < g->nlayers; ++k)
+            g->max_layer = std::max(g->max_layer, layer_tab[k + 1] - layer_tab[k]);
+        layer_tab.insert(layer_tab.end(), layer_chk.begin(), layer_chk.end());
+        g->layer_of = (int*)malloc(sizeof(int) * (size_t)C);
+        if (!g->layer_of) { (void)hipFree(g->dev); free(g); return GNND_ERR_ALLOC; }
+        memcpy(g->layer_of, layer_of.data(), sizeof(int) * (size_t)C);
+        err = hipMalloc((void**)&g->layer_dev, sizeof(int) * layer_tab.size());
+        if (err == hipSuccess) {
+            err = hipMemcpy(g->layer_dev, layer_tab.data(), sizeof(int) * layer_tab.size(),
+                            hipMemcpyHostToDevice);
+            if (err != hipSuccess) (void)hipFree(g->layer_dev);
+        }
+        if (err != hipSuccess) {
+            (void)hipFree(g->dev);
+            free(g->layer_of);
+            free(g);
+            return set_hip_error(err);
+        }
+    }
     *out = g;
     return GNND_OK;
 }
@@ -708,6 +736,9 @@ int destroy_graph(gnnd_graph* g) {
         const hipError_t e = hipFree(g->dcomp);
         if (err == hipSuccess) err = e;
     }
+    const hipError_t el = hipFree(g->layer_dev);
+    if (err == hipSuccess) err = el;
+    free(g->layer_of);
     const hipError_t e = hipFree(g->dev);
     if (err == hipSuccess) err = e;
     free(g);
@@ -827,6 +858,22 @@ extern "C" int gnnd_graph_components(const gnnd_graph* g, int32_t* h_ncomp) {
     if (!g || !h_ncomp) return GNND_ERR_INVALID_ARG;
     *h_ncomp = g->ncomp;
     return GNND_OK;
+}
+
+extern "C" int gnnd_graph_layers(const gnnd_graph* g, int32_t* h_nlayers,
+                                 int32_t* h_layer_of_check) {
+    if (!g || !h_nlayers) return GNND_ERR_INVALID_ARG;
+    *h_nlayers = g->nlayers;
+    if (h_layer_of_check)
+        for (int c = 0; c < g->view.C; ++c) h_layer_of_check[c] = g->layer_of[c];
+    return GNND_OK;
+}
+
+extern "C" int gnnd_graph_layers_host(const int64_t* h_var, const int64_t* h_chk,
+                                      int64_t num_edges, int32_t V, int32_t C, int32_t* h_nlayers,
+                                      int32_t* h_layer_of_check) {
+    return gnnd_graph_layers_host_checked(h_var, h_chk, num_edges, V, C, h_nlayers,
+                                          h_layer_of_check);
 }
 
 extern "C" int gnnd_graph_set_split(gnnd_graph* g, int32_t enable) {

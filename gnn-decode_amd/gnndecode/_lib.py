@@ -98,6 +98,21 @@ SIGNATURES = {
     'gnnd_bposd_host': (_int, [_c_i64p, _c_i64p, _i64, _i32, _i32, _int, _vp, ctypes.c_double,
                                ctypes.c_double, _i32, _i32, _int, _int, _i32, _vp, _vp, _c_i32p,
                                _c_i32p, _vp, _c_i32p, _c_i32p, _i64]),
+    'gnnd_graph_layers': (_int, [_vp, _c_i32p, _c_i32p]),
+    'gnnd_graph_layers_host': (_int, [_c_i64p, _c_i64p, _i64, _i32, _i32, _c_i32p, _c_i32p]),
+    'gnnd_minsum_layered': (_int, [_vp, _int, _vp, ctypes.c_double, ctypes.c_double, _i32, _i32,
+                                   _vp, _vp, _vp, _vp, _i64, _vp]),
+    'gnnd_minsum_layered_host': (_int, [_c_i64p, _c_i64p, _i64, _i32, _i32, _int, _vp,
+                                        ctypes.c_double, ctypes.c_double, _i32, _i32, _vp, _vp,
+                                        _c_i32p, _c_i32p, _i64]),
+    'gnnd_minsum_layered_plan': (_int, [_vp, _int, _c_i32p]),
+    'gnnd_bposd_layered': (_int, [_vp, _int, _vp, ctypes.c_double, ctypes.c_double, _i32, _i32,
+                                  _int, _int, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                  _i64, _vp]),
+    'gnnd_bposd_layered_host': (_int, [_c_i64p, _c_i64p, _i64, _i32, _i32, _int, _vp,
+                                       ctypes.c_double, ctypes.c_double, _i32, _i32, _int, _int,
+                                       _i32, _vp, _vp, _c_i32p, _c_i32p, _vp, _c_i32p, _c_i32p,
+                                       _i64]),
     'gnnd_v24_check_mlp_table': (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     'gnnd_adam_step': (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double,
                               ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp]),

@@ -63,6 +63,15 @@ class TannerGraph:
         _lib.call('gnnd_graph_components', self._handle, ctypes.byref(n))
         return int(n.value)
 
+    def layers(self):
+        """layer_of_check, int32 [C]: the greedy layers of the layered min-sum schedule
+        (gnnd_graph_layers; ops.minsum(..., schedule='layered') visits the checks by (layer, c))."""
+        n = ctypes.c_int32()
+        layer = np.empty(self.C, np.int32)
+        _lib.call('gnnd_graph_layers', self._handle, ctypes.byref(n),
+                  layer.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+        return layer
+
     def set_split(self, enable):
         """Use (default) or bypass the component split for this graph (A/B and tests)."""
         _lib.call('gnnd_graph_set_split', self._handle, int(bool(enable)))

@@ -28,6 +28,10 @@ a custom op costs more than the 0.47 ms headline kernel, measured r02n):
   gnnd::bposd_out(graph_id, x, iters, alpha, beta, early_stop, base, method, order, ehat, status,
       choice, iters_used, bp_status, pred, llr)                     the same, mutating
 
+  gnnd::minsum_layered, gnnd::minsum_layered_out, gnnd::bposd_layered, gnnd::bposd_layered_out
+      minsum / bposd on the layered schedule (gnnd_minsum_layered, gnnd_bposd_layered): the
+      signatures, outputs and fake kernels of the flooding ops
+
 The single-codeword Tanner graph is a device object owned by libgnnd, not a tensor: ops
 take the integer id that `register_graph` hands out (TannerGraph does this on creation;
 -1 = no graph: the generic kernels).  Implementations are the ctypes launches in
@@ -349,3 +353,73 @@ def bposd_out(graph_id: int, x: Tensor, iters: int, alpha: float, beta: float, e
 def _bposd_out_fake(graph_id, x, iters, alpha, beta, early_stop, base, method, order, ehat, status,
                     choice, iters_used, bp_status, pred, llr):
     return None
+
+
+# ---------------------------------------------------------------------------------------
+# the layered schedule: the same signatures, outputs and fake kernels as the flooding ops
+# ---------------------------------------------------------------------------------------
+@torch.library.custom_op('gnnd::minsum_layered', mutates_args=(), device_types='cuda')
+def minsum_layered(graph_id: int, x: Tensor, iters: int, alpha: float, beta: float,
+                   early_stop: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    from . import ops
+    g = graph_of(graph_id)
+    x = x.contiguous()
+    B = x.numel() // g.N
+    pred = torch.empty(B * g.V, 1, dtype=x.dtype, device=x.device)
+    llr = torch.empty(B * g.V, 1, dtype=x.dtype, device=x.device)
+    iters_used = torch.empty(B, dtype=torch.int32, device=x.device)
+    status = torch.empty(B, dtype=torch.int32, device=x.device)
+    ops._minsum_impl(g, x, iters, alpha, beta, early_stop, pred, llr, iters_used, status,
+                     schedule='layered')
+    return pred, llr, iters_used, status
+
+
+minsum_layered.register_fake(_minsum_fake)
+
+
+@torch.library.custom_op('gnnd::minsum_layered_out',
+                         mutates_args=('pred', 'llr', 'iters_used', 'status'), device_types='cuda')
+def minsum_layered_out(graph_id: int, x: Tensor, iters: int, alpha: float, beta: float,
+                       early_stop: bool, pred: Tensor, llr: Tensor, iters_used: Tensor,
+                       status: Tensor) -> None:
+    from . import ops
+    ops._minsum_impl(graph_of(graph_id), x.contiguous(), iters, alpha, beta, early_stop, pred,
+                     llr, iters_used, status, schedule='layered')
+
+
+minsum_layered_out.register_fake(_minsum_out_fake)
+
+
+@torch.library.custom_op('gnnd::bposd_layered', mutates_args=(), device_types='cuda')
+def bposd_layered(graph_id: int, x: Tensor, iters: int, alpha: float, beta: float,
+                  early_stop: bool, base: str, method: str, order: int
+                  ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from . import ops
+    g = graph_of(graph_id)
+    x = x.contiguous()
+    B = x.numel() // g.N
+    ehat, pred, llr = (torch.empty(B * g.V, 1, dtype=x.dtype, device=x.device) for _ in range(3))
+    status, choice, iters_used, bp_status = (torch.empty(B, dtype=torch.int32, device=x.device)
+                                             for _ in range(4))
+    ops._bposd_impl(g, x, iters, alpha, beta, early_stop, base, method, order, ehat, status, choice,
+                    iters_used, bp_status, pred, llr, schedule='layered')
+    return ehat, status, choice, iters_used, bp_status, pred, llr
+
+
+bposd_layered.register_fake(_bposd_fake)
+
+
+@torch.library.custom_op('gnnd::bposd_layered_out',
+                         mutates_args=('ehat', 'status', 'choice', 'iters_used', 'bp_status',
+                                       'pred', 'llr'), device_types='cuda')
+def bposd_layered_out(graph_id: int, x: Tensor, iters: int, alpha: float, beta: float,
+                      early_stop: bool, base: str, method: str, order: int, ehat: Tensor,
+                      status: Tensor, choice: Tensor, iters_used: Tensor, bp_status: Tensor,
+                      pred: Tensor, llr: Tensor) -> None:
+    from . import ops
+    ops._bposd_impl(graph_of(graph_id), x.contiguous(), iters, alpha, beta, early_stop, base, method,
+                    order, ehat, status, choice, iters_used, bp_status, pred, llr,
+                    schedule='layered')
+
+
+bposd_layered_out.register_fake(_bposd_out_fake)

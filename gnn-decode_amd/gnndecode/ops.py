@@ -751,9 +751,20 @@ def _minsum_check_params(iters, alpha, beta):
     return alpha, beta
 
 
-def minsum(graph, x, iters, alpha=0.75, beta=0.0, early_stop=True, out=None):
-    """Normalized / offset min-sum BP on the flooding schedule, one HIP launch (gnnd_minsum,
-    defined in include/gnnd.h): x [B*N(,1)] the decoder input (priors at the variable rows, the
+def _schedule_suffix(schedule):
+    """'' for the flooding schedule, '_layered' for the layered one: the suffix of the C entry
+    points and of the gnnd:: torch ops."""
+    if schedule == 'flooding':
+        return ''
+    if schedule == 'layered':
+        return '_layered'
+    raise ValueError(f"schedule must be 'flooding' or 'layered', got {schedule!r}")
+
+
+def minsum(graph, x, iters, alpha=0.75, beta=0.0, early_stop=True, out=None, schedule='flooding'):
+    """Normalized / offset min-sum BP, one HIP launch (gnnd_minsum on the flooding schedule,
+    gnnd_minsum_layered with schedule='layered': the checks visited layer by layer, each seeing
+    the posteriors the layers before it just updated; both defined in include/gnnd.h): x [B*N(,1)] the decoder input (priors at the variable rows, the
     syndrome at the check rows as for osd0) -> (pred, llr, iters_used, status).  Check messages
     are max(alpha * min|q| - beta, 0) with the sign product; with early_stop a codeword stops at
     the first iteration whose hard decision satisfies its syndrome.  pred [B*V, 1] is
@@ -765,12 +776,15 @@ def minsum(graph, x, iters, alpha=0.75, beta=0.0, early_stop=True, out=None):
     None to skip it (returned as None)."""
     alpha, beta = _minsum_check_params(iters, alpha, beta)
     early_stop = bool(early_stop)
+    suffix = _schedule_suffix(schedule)
     if torch.compiler.is_compiling():
         if out is None:
-            return torch.ops.gnnd.minsum(graph.gid, x, iters, alpha, beta, early_stop)
+            return getattr(torch.ops.gnnd, 'minsum' + suffix)(graph.gid, x, iters, alpha, beta,
+                                                              early_stop)
         if len(out) != 4 or any(o is None for o in out):
             raise ValueError('traced minsum needs out = (pred, llr, iters_used, status)')
-        torch.ops.gnnd.minsum_out(graph.gid, x, iters, alpha, beta, early_stop, *out)
+        getattr(torch.ops.gnnd, 'minsum' + suffix + '_out')(graph.gid, x, iters, alpha, beta,
+                                                            early_stop, *out)
         return out
     _require_gpu(x)
     if x.dtype not in (torch.float32, torch.float64):
@@ -794,23 +808,26 @@ def minsum(graph, x, iters, alpha=0.75, beta=0.0, early_stop=True, out=None):
     for t in out[2:]:
         if t is not None and (t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
             raise ValueError(f'iters_used / status must be contiguous int32 [{B}]')
-    _minsum_impl(graph, x, iters, alpha, beta, early_stop, *out)
+    _minsum_impl(graph, x, iters, alpha, beta, early_stop, *out, schedule=schedule)
     return tuple(out)
 
 
-def _minsum_impl(graph, x, iters, alpha, beta, early_stop, pred, llr, iters_used, status):
-    """gnnd::minsum / gnnd::minsum_out implementation (gnndecode.library)."""
-    _lib.call('gnnd_minsum', graph.handle, dtype_code(x.dtype), _ptr(x), alpha, beta, iters,
+def _minsum_impl(graph, x, iters, alpha, beta, early_stop, pred, llr, iters_used, status,
+                 schedule='flooding'):
+    """gnnd::minsum[_layered] / gnnd::minsum[_layered]_out implementation (gnndecode.library)."""
+    _lib.call('gnnd_minsum' + _schedule_suffix(schedule), graph.handle, dtype_code(x.dtype), _ptr(x), alpha, beta, iters,
               int(early_stop), _ptr(pred), _ptr(llr), _ptr(iters_used), _ptr(status),
               x.numel() // graph.N, current_stream(x.device))
 
 
-def minsum_host(H, x, iters, alpha=0.75, beta=0.0, early_stop=True):
-    """The host mirror of minsum (gnnd_minsum_host): numpy in, numpy out, no device.  H [V, C],
-    x [B*N] float32 or float64 -> (pred, llr like x's dtype [B*V], iters_used, status int32 [B])."""
+def minsum_host(H, x, iters, alpha=0.75, beta=0.0, early_stop=True, schedule='flooding'):
+    """The host mirror of minsum (gnnd_minsum_host, gnnd_minsum_layered_host with
+    schedule='layered'): numpy in, numpy out, no device.  H [V, C], x [B*N] float32 or float64
+    -> (pred, llr like x's dtype [B*V], iters_used, status int32 [B])."""
     import numpy as np
     from .graph import edge_list
     alpha, beta = _minsum_check_params(iters, alpha, beta)
+    suffix = _schedule_suffix(schedule)
     H = np.asarray(H)
     V, C = H.shape
     x = np.ascontiguousarray(x)
@@ -825,11 +842,33 @@ def minsum_host(H, x, iters, alpha=0.75, beta=0.0, early_stop=True):
     iters_used = np.empty(B, np.int32)
     status = np.empty(B, np.int32)
     P64, P32 = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
-    _lib.call('gnnd_minsum_host', var.ctypes.data_as(P64), chk.ctypes.data_as(P64), var.size, V, C,
+    _lib.call(f'gnnd_minsum{suffix}_host', var.ctypes.data_as(P64), chk.ctypes.data_as(P64), var.size, V, C,
               _lib.F32 if x.dtype == np.float32 else _lib.F64, x.ctypes.data, alpha, beta, iters,
               int(bool(early_stop)), pred.ctypes.data, llr.ctypes.data,
               iters_used.ctypes.data_as(P32), status.ctypes.data_as(P32), B)
     return pred, llr, iters_used, status
+
+
+def minsum_layered_plan(graph, dtype):
+    """The layered kernel's plan for `dtype` (gnnd_minsum_layered_plan) -> dict(layers,
+    largest_layer, lanes_per_codeword, codewords_per_workgroup)."""
+    plan = (ctypes.c_int32 * 4)()
+    _lib.call('gnnd_minsum_layered_plan', graph.handle, dtype_code(dtype), plan)
+    return dict(zip(('layers', 'largest_layer', 'lanes_per_codeword', 'codewords_per_workgroup'),
+                    (int(p) for p in plan)))
+
+
+def layers_host(H):
+    """The greedy layers of H [V, C] on the host (gnnd_graph_layers_host) -> layer_of_check
+    int32 [C]."""
+    import numpy as np
+    V, C, var, chk, vp, cp = _host_graph(H)
+    n = ctypes.c_int32()
+    layer = np.empty(C, np.int32)
+    _lib.call('gnnd_graph_layers_host', vp, cp, var.size, V, C, ctypes.byref(n),
+              layer.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    assert C == 0 or int(layer.max()) + 1 == n.value
+    return layer
 
 
 # ---------------------------------------------------------------------------------------
@@ -926,25 +965,28 @@ def _osd_gated_impl(graph, x, pred, gate, base, method, order, llr, ehat, status
 
 
 def bposd(graph, x, iters, alpha=0.75, beta=0.0, early_stop=True, base='zero', method='cs',
-          order=10, out=None, work=None):
+          order=10, out=None, work=None, schedule='flooding'):
     """The BP+OSD decoder in one call (gnnd_bposd): minsum, then osd_gated with the min-sum status
     as the gate and the min-sum llr as the pass-through decision, three launches on the current
     stream, no host sync.  -> (ehat, status, choice, iters_used, bp_status, pred, llr): where
     bp_status is 0 ehat is min-sum's hard decision, which satisfies the syndrome, and choice is
     -1; elsewhere ehat / status / choice are osd's.  Everything but pred is bit-reproducible
     (bposd_host gives the same bits).  `out`: the seven tensors to write into, choice and
-    iters_used may be None to skip them; `work` as for osd_gated."""
+    iters_used may be None to skip them; `work` as for osd_gated.  schedule='layered' runs the
+    min-sum stage on the layered schedule (gnnd_bposd_layered, mirror bposd_host(...,
+    schedule='layered')); the OSD stage is the same."""
     alpha, beta = _minsum_check_params(iters, alpha, beta)
     early_stop = bool(early_stop)
     _osd_check_method(base, method, order)
+    suffix = _schedule_suffix(schedule)
     if torch.compiler.is_compiling():
         if out is None:
-            return torch.ops.gnnd.bposd(graph.gid, x, iters, alpha, beta, early_stop, base, method,
-                                        order)
+            return getattr(torch.ops.gnnd, 'bposd' + suffix)(graph.gid, x, iters, alpha, beta,
+                                                             early_stop, base, method, order)
         if len(out) != 7 or any(o is None for o in out):
             raise ValueError('traced bposd needs all seven out tensors')
-        torch.ops.gnnd.bposd_out(graph.gid, x, iters, alpha, beta, early_stop, base, method, order,
-                                 *out)
+        getattr(torch.ops.gnnd, 'bposd' + suffix + '_out')(graph.gid, x, iters, alpha, beta,
+                                                           early_stop, base, method, order, *out)
         return out
     _require_gpu(x)
     if x.dtype not in (torch.float32, torch.float64):
@@ -973,16 +1015,16 @@ def bposd(graph, x, iters, alpha=0.75, beta=0.0, early_stop=True, base='zero', m
         if t is not None and (t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
             raise ValueError(f'status / choice / iters_used / bp_status must be contiguous int32 [{B}]')
     _bposd_impl(graph, x, iters, alpha, beta, early_stop, base, method, order, ehat, status, choice,
-                iters_used, bp_status, pred, llr, work)
+                iters_used, bp_status, pred, llr, work, schedule)
     return tuple(out)
 
 
 def _bposd_impl(graph, x, iters, alpha, beta, early_stop, base, method, order, ehat, status, choice,
-                iters_used, bp_status, pred, llr, work=None):
-    """gnnd::bposd / gnnd::bposd_out implementation (gnndecode.library)."""
+                iters_used, bp_status, pred, llr, work=None, schedule='flooding'):
+    """gnnd::bposd[_layered] / gnnd::bposd[_layered]_out implementation (gnndecode.library)."""
     B = x.numel() // graph.N
     work, nbytes = _gated_work(work, B, x.device)
-    _lib.call('gnnd_bposd', graph.handle, dtype_code(x.dtype), _ptr(x), alpha, beta, iters,
+    _lib.call('gnnd_bposd' + _schedule_suffix(schedule), graph.handle, dtype_code(x.dtype), _ptr(x), alpha, beta, iters,
               int(early_stop), _lib.OSD_BASE[base], _lib.OSD_METHOD[method], order, _ptr(pred),
               _ptr(llr), _ptr(iters_used), _ptr(bp_status), _ptr(ehat), _ptr(status), _ptr(choice),
               _ptr(work), nbytes, B, current_stream(x.device))
@@ -1028,11 +1070,13 @@ def osd_gated_host(H, x, pred, gate, base='zero', method='cs', order=10, llr=Non
 
 
 def bposd_host(H, x, iters, alpha=0.75, beta=0.0, early_stop=True, base='zero', method='cs',
-               order=10):
-    """The host mirror of bposd (gnnd_bposd_host): numpy in, numpy out, no device.  -> (ehat,
-    status, choice, iters_used, bp_status, pred, llr)."""
+               order=10, schedule='flooding'):
+    """The host mirror of bposd (gnnd_bposd_host, gnnd_bposd_layered_host with
+    schedule='layered'): numpy in, numpy out, no device.  -> (ehat, status, choice, iters_used,
+    bp_status, pred, llr)."""
     import numpy as np
     alpha, beta = _minsum_check_params(iters, alpha, beta)
+    suffix = _schedule_suffix(schedule)
     _osd_check_method(base, method, order)
     V, C, var, chk, vp, cp = _host_graph(H)
     x = np.ascontiguousarray(x)
@@ -1044,7 +1088,7 @@ def bposd_host(H, x, iters, alpha=0.75, beta=0.0, early_stop=True, base='zero', 
     ehat, pred, llr = (np.empty(B * V, x.dtype) for _ in range(3))
     status, choice, iters_used, bp_status = (np.empty(B, np.int32) for _ in range(4))
     P32 = ctypes.POINTER(ctypes.c_int32)
-    _lib.call('gnnd_bposd_host', vp, cp, var.size, V, C,
+    _lib.call(f'gnnd_bposd{suffix}_host', vp, cp, var.size, V, C,
               _lib.F32 if x.dtype == np.float32 else _lib.F64, x.ctypes.data, alpha, beta, iters,
               int(bool(early_stop)), _lib.OSD_BASE[base], _lib.OSD_METHOD[method], order,
               pred.ctypes.data, llr.ctypes.data, iters_used.ctypes.data_as(P32),

@@ -578,6 +578,71 @@ int gnnd_bposd_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edge
                     int32_t* h_bp_status, void* h_ehat, int32_t* h_status, int32_t* h_choice,
                     int64_t batch);
 
+/* ---- layered-schedule min-sum BP and the layered one-call BP+OSD decoder ---------------------
+ * gnnd_minsum on the layered (serial, check-sequential) schedule: the checks are visited one
+ * after another and each sees the variable posteriors the checks before it just updated, the
+ * usual way to reach a decision in about half the iterations of the flooding schedule.
+ * Layers.  Computed once per graph on the host, in gnnd_graph_create.  Checks are taken in
+ * ascending c; layer(c) is the smallest k >= 0 such that no check c' < c with layer(c') == k
+ * shares a variable with c.  The layered order is the checks sorted by (layer, c).  Two checks of
+ * one layer share no variable.  gnnd_graph_layers returns the number of layers and, where
+ * h_layer_of_check [C] is not NULL, layer(c); gnnd_graph_layers_host is the same rule on the edge
+ * list gnnd_graph_create takes, with no device (both: a NULL graph / edge list / h_nlayers is
+ * GNND_ERR_INVALID_ARG; the host form checks the edge list as gnnd_minsum_host does).
+ * Loop.  Per codeword b, T = float / double; a, b, t_c, l_v, the edge order and the x / output
+ * layouts exactly as in gnnd_minsum:
+ *   L_v = l_v for every variable;  r_e = +0 for every edge
+ *   for it = 1 .. iters:
+ *     for c in the layered order:
+ *       q_e = L_v(e) - r_e                for e in E(c)     (one subtraction in T)
+ *       neg, m, d = round(round(a * m) - b), mag, r'_e      gnnd_minsum's check step over these
+ *                                                            q_e, literally (ties, -0.0, two
+ *                                                            roundings, no fused multiply-add)
+ *       L_v(e) = q_e + r'_e ;  r_e = r'_e  for e in E(c)     (one addition in T)
+ *     h_v = (L_v < 0);  ok = (H^T h == t on every check);  if early_stop and ok: stop
+ * The checks of a layer touch disjoint L_v, so any order or parallelism inside a layer gives the
+ * bits of this serial statement; the kernel relies on that.
+ * Outputs, NULL rules, argument checks, non-finite behaviour, GNND_ERR_* conditions and batch 0
+ * follow gnnd_minsum word for word, with one exception: the per-codeword LDS tile is (E + V)
+ * values of T (no separate prior array), refused with GNND_ERR_UNSUPPORTED over 64 KiB.  d_llr,
+ * d_iters and d_status are bit-reproducible in both dtypes; d_out is outside the contract in
+ * GNND_F32 and uses gnnd_bposd's fixed exponential in GNND_F64.  One launch on `stream`, no host
+ * sync (capturable): a codeword gets G lanes of a wave, G the power of two covering the largest
+ * layer, clamped to [8, 64] (raised where 64 / G tiles would not fit in 64 KiB), and a wave holds
+ * 64 / G codewords.  gnnd_minsum_layered_plan reports h_plan4 = {layers, checks in the largest
+ * layer, lanes per codeword, codewords per workgroup} for `dtype` (GNND_ERR_UNSUPPORTED where
+ * gnnd_minsum_layered would refuse the graph).  gnnd_minsum_layered_host is the host mirror: the
+ * same definition, the same bits in llr / iters / status.
+ * gnnd_bposd_layered is gnnd_bposd with gnnd_minsum_layered as its first stage: the layered
+ * min-sum, then the unchanged gnnd_osd_gated, three launches on `stream`, no host sync; arguments,
+ * refusals (all decided before the first launch) and guarantees as for gnnd_bposd.
+ * gnnd_bposd_layered_host is its mirror; in GNND_F64 d_pred goes through the same fixed
+ * exponential on both sides, so every output is the same bits on the device and in the mirror. */
+int gnnd_graph_layers(const gnnd_graph* g, int32_t* h_nlayers, int32_t* h_layer_of_check);
+int gnnd_graph_layers_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                           int32_t num_var, int32_t num_chk, int32_t* h_nlayers,
+                           int32_t* h_layer_of_check);
+int gnnd_minsum_layered(const gnnd_graph* g, int dtype, const void* d_x, double alpha, double beta,
+                        int32_t iters, int32_t early_stop, void* d_out, void* d_llr,
+                        int32_t* d_iters, int32_t* d_status, int64_t batch, void* stream);
+int gnnd_minsum_layered_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                             int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                             double alpha, double beta, int32_t iters, int32_t early_stop,
+                             void* h_out, void* h_llr, int32_t* h_iters, int32_t* h_status,
+                             int64_t batch);
+int gnnd_minsum_layered_plan(const gnnd_graph* g, int dtype, int32_t* h_plan4);
+int gnnd_bposd_layered(const gnnd_graph* g, int dtype, const void* d_x, double alpha, double beta,
+                       int32_t iters, int32_t early_stop, int base, int method, int32_t order,
+                       void* d_pred, void* d_llr, int32_t* d_iters, int32_t* d_bp_status,
+                       void* d_ehat, int32_t* d_status, int32_t* d_choice, void* d_work,
+                       int64_t work_bytes, int64_t batch, void* stream);
+int gnnd_bposd_layered_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                            int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                            double alpha, double beta, int32_t iters, int32_t early_stop, int base,
+                            int method, int32_t order, void* h_pred, void* h_llr, int32_t* h_iters,
+                            int32_t* h_bp_status, void* h_ehat, int32_t* h_status,
+                            int32_t* h_choice, int64_t batch);
+
 /* Adam (torch.optim.Adam update order, amsgrad/maximize off) on one flat parameter buffer of
  * n values with its two moment buffers; *d_step is the device-resident step count (double,
  * incremented by the call), so a whole training step with the update can be captured in one
