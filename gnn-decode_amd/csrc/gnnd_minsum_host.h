@@ -40,17 +40,27 @@ inline double gnnd_exp_f64_device(double x) {
     return std::ldexp(p, (int)k);
 }
 
-// out, llr, iters_out and status may each be null here (the checked entry requires out).
-// device_exp: the fp64 soft output through gnnd_exp_f64_device instead of the host library's exp
-// (gnnd_bposd_host; gnnd_minsum_host keeps the library's)
-template <typename T>
-int gnnd_minsum_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges, int V,
-                          int C, const T* x, double alpha, double beta, int iters, int early_stop,
-                          T* out, T* llr, int32_t* iters_out, int32_t* status, int64_t batch,
-                          bool device_exp = false) {
+// The graph tables of the host mirrors, built from the edge list gnnd_graph_create takes, with its
+// checks: more than 65535 edges / variables / checks or a check of degree < 2 is
+// GNND_ERR_UNSUPPORTED, an id out of range or an edge list not sorted by (v, c) (or with a
+// duplicate) GNND_ERR_GRAPH.  gnnd_minsum_host and gnnd_relay_host share it.
+struct GnndHostGraph {
+    int E = 0;
+    std::vector<int> vptr, cptr;    // [V + 1], [C + 1]: edge ranges of the variables / checks
+    std::vector<int> cedge;         // [E] edge ids check by check, ascending inside a check
+    std::vector<int> evar;          // [E] the variable of every edge
+};
+
+inline int gnnd_host_graph_build(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                                 int V, int C, GnndHostGraph& hg) {
     if (num_edges > 65535 || V > 65535 || C > 65535) return GNND_ERR_UNSUPPORTED;
     const int E = (int)num_edges;
-    std::vector<int> vptr(V + 1, 0), cptr(C + 1, 0), cedge(E), evar(E);
+    hg.E = E;
+    hg.vptr.assign(V + 1, 0);
+    hg.cptr.assign(C + 1, 0);
+    hg.cedge.assign(E, 0);
+    hg.evar.assign(E, 0);
+    std::vector<int>&vptr = hg.vptr, &cptr = hg.cptr, &cedge = hg.cedge, &evar = hg.evar;
     for (int e = 0; e < E; ++e) {
         const int64_t v = h_var[e], c = h_chk[e];
         if (v < 0 || v >= V || c < 0 || c >= C) return GNND_ERR_GRAPH;
@@ -64,10 +74,24 @@ int gnnd_minsum_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t nu
         if (cptr[c + 1] < 2) return GNND_ERR_UNSUPPORTED;
     for (int v = 0; v < V; ++v) vptr[v + 1] += vptr[v];
     for (int c = 0; c < C; ++c) cptr[c + 1] += cptr[c];
-    {
-        std::vector<int> fill(cptr.begin(), cptr.end() - 1);
-        for (int e = 0; e < E; ++e) cedge[fill[h_chk[e]]++] = e;
-    }
+    std::vector<int> fill(cptr.begin(), cptr.end() - 1);
+    for (int e = 0; e < E; ++e) cedge[fill[h_chk[e]]++] = e;
+    return GNND_OK;
+}
+
+// out, llr, iters_out and status may each be null here (the checked entry requires out).
+// device_exp: the fp64 soft output through gnnd_exp_f64_device instead of the host library's exp
+// (gnnd_bposd_host; gnnd_minsum_host keeps the library's)
+template <typename T>
+int gnnd_minsum_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges, int V,
+                          int C, const T* x, double alpha, double beta, int iters, int early_stop,
+                          T* out, T* llr, int32_t* iters_out, int32_t* status, int64_t batch,
+                          bool device_exp = false) {
+    GnndHostGraph hg;
+    const int rc = gnnd_host_graph_build(h_var, h_chk, num_edges, V, C, hg);
+    if (rc != GNND_OK) return rc;
+    const int E = hg.E;
+    const std::vector<int>&vptr = hg.vptr, &cptr = hg.cptr, &cedge = hg.cedge, &evar = hg.evar;
     const T a = (T)alpha, bt = (T)beta;
     const int N = V + C;
     std::vector<T> msg(E), L(V);

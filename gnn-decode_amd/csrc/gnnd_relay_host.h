@@ -1,0 +1,158 @@
+// gnnd_relay_host.h — host mirror of gnnd_relay (include/gnnd.h): relay min-sum BP, a chain of
+// memory-strength legs that keeps the lightest solution, in plain C++.  No HIP types: a plain host
+// compiler builds it, so a stand-alone program can run it under host sanitizers
+// (tools/relay_host_check.cpp).  Same definition as the kernel in gnnd_relay.hip, bit for bit in
+// every output: gnnd_minsum_host's check step, c * l + g * M as three roundings (build this header's
+// translation unit with -ffp-contract=off), the variable sum over E(v) in ascending edge order, the
+// weight through the fixed 64-partial tree.
+#pragma once
+#include "gnnd_minsum_host.h"
+
+// legs / iters0 / iters_leg / stop_after / alpha / beta within the contract's limits; the
+// iteration total must fit the int32 d_iters reports
+inline bool gnnd_relay_params_ok(double alpha, double beta, int32_t legs, int32_t iters0,
+                                 int32_t iters_leg, int32_t stop_after) {
+    if (legs < 1 || iters0 < 1 || iters_leg < 1 || stop_after < 1) return false;
+    if ((int64_t)iters0 + (int64_t)(legs - 1) * iters_leg > 2147483647LL) return false;
+    return gnnd_minsum_params_ok(alpha, beta, 1, 1);
+}
+
+// weight(h) of the contract: 64 partials over v = j (mod 64) in ascending v, then the six-step
+// butterfly p_j = p_j + p_{j xor s}, s = 32 .. 1; every p_j ends as the same value, w = p_0
+template <typename T>
+T gnnd_relay_weight(const T* L, const T* l, int V) {
+    T p[64], n[64];
+    for (int j = 0; j < 64; ++j) {
+        T s = T(0);
+        for (int v = j; v < V; v += 64) s = s + (L[v] < T(0) ? l[v] : T(0));
+        p[j] = s;
+    }
+    for (int s = 32; s >= 1; s >>= 1) {
+        for (int j = 0; j < 64; ++j) n[j] = p[j] + p[j ^ s];
+        for (int j = 0; j < 64; ++j) p[j] = n[j];
+    }
+    return p[0];
+}
+
+// every output but ehat may be null
+template <typename T>
+int gnnd_relay_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges, int V,
+                         int C, const T* x, const T* gammas, int legs, int iters0, int iters_leg,
+                         int stop_after, double alpha, double beta, T* ehat, T* llr,
+                         int32_t* iters_out, int32_t* status, int32_t* leg_out, int32_t* nsol_out,
+                         int64_t batch) {
+    GnndHostGraph hg;
+    const int rc = gnnd_host_graph_build(h_var, h_chk, num_edges, V, C, hg);
+    if (rc != GNND_OK) return rc;
+    const int E = hg.E;
+    const std::vector<int>&vptr = hg.vptr, &cptr = hg.cptr, &cedge = hg.cedge, &evar = hg.evar;
+    const T a = (T)alpha, bt = (T)beta;
+    const int N = V + C;
+    std::vector<T> msg(E), L(V), A(V), best(V);
+    for (int64_t b = 0; b < batch; ++b) {
+        const T* xv = x + b * N;
+        const T* xc = xv + V;
+        for (int v = 0; v < V; ++v) L[v] = xv[v];                    // M_v = l_v
+        int total = 0, nsol = 0, bestk = -1;
+        T bestw = T(0);
+        for (int k = 0; k < legs; ++k) {
+            const T* g = gammas + (size_t)k * V;
+            // A_v: the prior term of the leg (l_v itself where g_v == 0: selected, not computed)
+            for (int v = 0; v < V; ++v) {
+                const T c = T(1) - g[v];
+                const T cl = c * xv[v];
+                A[v] = g[v] == T(0) ? xv[v] : cl;
+            }
+            for (int e = 0; e < E; ++e) {
+                const int v = evar[e];
+                const T gm = g[v] * L[v];
+                const T lam = A[v] + gm;
+                msg[e] = g[v] == T(0) ? A[v] : lam;
+            }
+            const int Tk = k == 0 ? iters0 : iters_leg;
+            for (int it = 0; it < Tk; ++it) {
+                ++total;
+                for (int c = 0; c < C; ++c) {
+                    T min1 = std::numeric_limits<T>::infinity(), min2 = min1;
+                    int arg = -1, par = xc[c] < T(0);
+                    for (int i = cptr[c]; i < cptr[c + 1]; ++i) {
+                        const T q = msg[cedge[i]];
+                        const T aq = std::fabs(q);
+                        par ^= (int)(q < T(0));
+                        if (aq < min1) { min2 = min1; min1 = aq; arg = cedge[i]; }
+                        else if (aq < min2) min2 = aq;
+                    }
+                    for (int i = cptr[c]; i < cptr[c + 1]; ++i) {
+                        const int e = cedge[i];
+                        const T q = msg[e];
+                        const T m = e == arg ? min2 : min1;
+                        const T am = a * m;
+                        const T d = am - bt;
+                        const T mag = d > T(0) ? d : T(0);
+                        msg[e] = (par ^ (int)(q < T(0))) ? -mag : mag;
+                    }
+                }
+                for (int v = 0; v < V; ++v) {
+                    const T gm = g[v] * L[v];
+                    const T lam = A[v] + gm;
+                    T s = g[v] == T(0) ? A[v] : lam;
+                    for (int e = vptr[v]; e < vptr[v + 1]; ++e) s = s + msg[e];
+                    L[v] = s;
+                    for (int e = vptr[v]; e < vptr[v + 1]; ++e) msg[e] = s - msg[e];
+                }
+                int ok = 1;
+                for (int c = 0; c < C; ++c) {
+                    int par = xc[c] < T(0);
+                    for (int i = cptr[c]; i < cptr[c + 1]; ++i) par ^= (int)(L[evar[cedge[i]]] < T(0));
+                    if (par) { ok = 0; break; }
+                }
+                if (ok) {
+                    const T w = gnnd_relay_weight(L.data(), xv, V);
+                    if (nsol == 0 || w < bestw) {                    // strict: a tie keeps the earlier
+                        bestw = w;
+                        bestk = k;
+                        best = L;
+                    }
+                    ++nsol;
+                    break;
+                }
+            }
+            if (nsol >= stop_after) break;
+        }
+        const T* src = nsol ? best.data() : L.data();
+        for (int v = 0; v < V; ++v) {
+            ehat[b * V + v] = src[v] < T(0) ? T(1) : T(0);
+            if (llr) llr[b * V + v] = src[v];
+        }
+        if (iters_out) iters_out[b] = total;
+        if (status) status[b] = nsol ? 0 : 1;
+        if (leg_out) leg_out[b] = bestk;
+        if (nsol_out) nsol_out[b] = nsol;
+    }
+    return GNND_OK;
+}
+
+inline int gnnd_relay_host_checked(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                                   int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                                   const void* h_gammas, int32_t legs, int32_t iters0,
+                                   int32_t iters_leg, int32_t stop_after, double alpha, double beta,
+                                   void* h_ehat, void* h_llr, int32_t* h_iters, int32_t* h_status,
+                                   int32_t* h_leg, int32_t* h_nsol, int64_t batch) {
+    if (!h_var || !h_chk || num_edges <= 0 || num_var <= 0 || num_chk <= 0 || batch < 0)
+        return GNND_ERR_INVALID_ARG;
+    if (!gnnd_relay_params_ok(alpha, beta, legs, iters0, iters_leg, stop_after))
+        return GNND_ERR_INVALID_ARG;
+    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
+    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    if (batch == 0) return GNND_OK;
+    if (!h_x || !h_gammas || !h_ehat) return GNND_ERR_INVALID_ARG;
+    if (dtype == GNND_F32)
+        return gnnd_relay_host_impl<float>(h_var, h_chk, num_edges, num_var, num_chk,
+                                           (const float*)h_x, (const float*)h_gammas, legs, iters0,
+                                           iters_leg, stop_after, alpha, beta, (float*)h_ehat,
+                                           (float*)h_llr, h_iters, h_status, h_leg, h_nsol, batch);
+    return gnnd_relay_host_impl<double>(h_var, h_chk, num_edges, num_var, num_chk,
+                                        (const double*)h_x, (const double*)h_gammas, legs, iters0,
+                                        iters_leg, stop_after, alpha, beta, (double*)h_ehat,
+                                        (double*)h_llr, h_iters, h_status, h_leg, h_nsol, batch);
+}

@@ -32,6 +32,12 @@ a custom op costs more than the 0.47 ms headline kernel, measured r02n):
       minsum / bposd on the layered schedule (gnnd_minsum_layered, gnnd_bposd_layered): the
       signatures, outputs and fake kernels of the flooding ops
 
+  gnnd::relay(graph_id, x, gammas, iters0, iters_leg, stop_after, alpha, beta)
+      -> (ehat, llr, iters_used, status, leg, nsol)   relay min-sum BP: memory-strength legs, the
+      lightest solution kept
+  gnnd::relay_out(graph_id, x, gammas, iters0, iters_leg, stop_after, alpha, beta, ehat, llr,
+      iters_used, status, leg, nsol)                  the same into its outputs (mutates)
+
 The single-codeword Tanner graph is a device object owned by libgnnd, not a tensor: ops
 take the integer id that `register_graph` hands out (TannerGraph does this on creation;
 -1 = no graph: the generic kernels).  Implementations are the ctypes launches in
@@ -423,3 +429,47 @@ def bposd_layered_out(graph_id: int, x: Tensor, iters: int, alpha: float, beta: 
 
 
 bposd_layered_out.register_fake(_bposd_out_fake)
+
+
+
+# ---------------------------------------------------------------------------------------
+# relay min-sum BP
+# ---------------------------------------------------------------------------------------
+@torch.library.custom_op('gnnd::relay', mutates_args=(), device_types='cuda')
+def relay(graph_id: int, x: Tensor, gammas: Tensor, iters0: int, iters_leg: int, stop_after: int,
+          alpha: float, beta: float) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from . import ops
+    g = graph_of(graph_id)
+    x = x.contiguous()
+    B = x.numel() // g.N
+    ehat = torch.empty(B * g.V, 1, dtype=x.dtype, device=x.device)
+    llr = torch.empty(B * g.V, 1, dtype=x.dtype, device=x.device)
+    ints = tuple(torch.empty(B, dtype=torch.int32, device=x.device) for _ in range(4))
+    ops._relay_impl(g, x, gammas.contiguous(), iters0, iters_leg, stop_after, alpha, beta, ehat,
+                    llr, *ints)
+    return (ehat, llr) + ints
+
+
+@relay.register_fake
+def _relay_fake(graph_id, x, gammas, iters0, iters_leg, stop_after, alpha, beta):
+    V, C, N, E = _DIMS[graph_id]
+    B = x.numel() // N
+    return ((x.new_empty(B * V, 1), x.new_empty(B * V, 1))
+            + tuple(x.new_empty(B, dtype=torch.int32) for _ in range(4)))
+
+
+@torch.library.custom_op('gnnd::relay_out',
+                         mutates_args=('ehat', 'llr', 'iters_used', 'status', 'leg', 'nsol'),
+                         device_types='cuda')
+def relay_out(graph_id: int, x: Tensor, gammas: Tensor, iters0: int, iters_leg: int,
+              stop_after: int, alpha: float, beta: float, ehat: Tensor, llr: Tensor,
+              iters_used: Tensor, status: Tensor, leg: Tensor, nsol: Tensor) -> None:
+    from . import ops
+    ops._relay_impl(graph_of(graph_id), x.contiguous(), gammas.contiguous(), iters0, iters_leg,
+                    stop_after, alpha, beta, ehat, llr, iters_used, status, leg, nsol)
+
+
+@relay_out.register_fake
+def _relay_out_fake(graph_id, x, gammas, iters0, iters_leg, stop_after, alpha, beta, ehat, llr,
+                    iters_used, status, leg, nsol):
+    return None

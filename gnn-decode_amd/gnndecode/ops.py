@@ -872,6 +872,132 @@ def layers_host(H):
 
 
 # ---------------------------------------------------------------------------------------
+# relay min-sum BP: memory-strength legs that keep the lightest solution (gnnd_relay)
+# ---------------------------------------------------------------------------------------
+def _relay_check_params(iters0, iters_leg, stop_after, alpha, beta, legs):
+    if iters_leg is None:
+        iters_leg = iters0
+    for name, val in (('iters0', iters0), ('iters_leg', iters_leg), ('stop_after', stop_after)):
+        if not isinstance(val, int) or isinstance(val, bool) or not 1 <= val <= 2 ** 31 - 1:
+            raise ValueError(f'{name} must be an integer >= 1, got {val!r}')
+    if legs < 1:
+        raise ValueError('gammas must hold at least one leg')
+    if iters0 + (legs - 1) * iters_leg > 2 ** 31 - 1:
+        raise ValueError('iters0 + (legs - 1) * iters_leg must fit an int32')
+    alpha, beta = _minsum_check_params(1, alpha, beta)
+    return iters_leg, alpha, beta
+
+
+def relay_gammas(V, legs, gamma0=0.125, center=0.21, width=0.9, seed=0, dtype=torch.float64,
+                 device=None):
+    """The usual relay memory strengths, [legs, V] in `dtype`: row 0 is `gamma0` on every variable,
+    the later rows are numpy.random.default_rng(seed).uniform(center - width / 2, center + width /
+    2, (legs - 1, V)) (disordered, partly negative), drawn in float64 and cast to `dtype`."""
+    import numpy as np
+    if not isinstance(legs, int) or isinstance(legs, bool) or legs < 1:
+        raise ValueError(f'legs must be an integer >= 1, got {legs!r}')
+    g = np.full((legs, V), float(gamma0), np.float64)
+    g[1:] = np.random.default_rng(seed).uniform(center - width / 2, center + width / 2,
+                                                (legs - 1, V))
+    return torch.from_numpy(g).to(dtype=dtype, device=device)
+
+
+def relay(graph, x, gammas, iters0, iters_leg=None, stop_after=1, alpha=0.75, beta=0.0, out=None):
+    """Relay min-sum BP, one HIP launch (gnnd_relay, defined in include/gnnd.h): min-sum with the
+    per-variable memory strengths gammas [legs, V] (relay_gammas makes the usual table), one row
+    per leg; leg 0 runs at most iters0 iterations, every later leg iters_leg (default iters0), each
+    from the posteriors of the leg before; a leg ends at its first hard decision that satisfies the
+    syndrome, the call after stop_after such solutions, and the lightest solution is kept.
+    x [B*N(,1)] as for minsum -> (ehat, llr, iters_used, status, leg, nsol): ehat [B*V, 1] exactly
+    0.0 / 1.0 and llr [B*V, 1] of the kept solution (of the last iteration where there is none),
+    iters_used [B] int32 all iterations executed, status [B] int32 0 where a solution was found
+    (ehat then satisfies the syndrome), leg [B] int32 the leg of the kept solution or -1, nsol [B]
+    int32 the solutions collected.  Every output is bit-reproducible (relay_host gives the same
+    bits).  No host sync; `out` = the six tensors to write into, each but ehat may be None to skip
+    it (returned as None)."""
+    if gammas.dim() != 2 or gammas.shape[1] != graph.V:
+        raise ValueError(f'gammas must be [legs, V] (V = {graph.V})')
+    legs = gammas.shape[0]
+    iters_leg, alpha, beta = _relay_check_params(iters0, iters_leg, stop_after, alpha, beta, legs)
+    if torch.compiler.is_compiling():
+        if out is None:
+            return torch.ops.gnnd.relay(graph.gid, x, gammas, iters0, iters_leg, stop_after, alpha,
+                                        beta)
+        if len(out) != 6 or any(o is None for o in out):
+            raise ValueError('traced relay needs out = (ehat, llr, iters_used, status, leg, nsol)')
+        torch.ops.gnnd.relay_out(graph.gid, x, gammas, iters0, iters_leg, stop_after, alpha, beta,
+                                 *out)
+        return out
+    _require_gpu(x, gammas)
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f'relay supports float32/float64, got {x.dtype}')
+    if gammas.dtype != x.dtype:
+        raise TypeError(f'gammas must have the dtype of x ({x.dtype}), got {gammas.dtype}')
+    x = x.contiguous()
+    gammas = gammas.contiguous()
+    B = x.numel() // graph.N
+    if x.numel() != B * graph.N:
+        raise ValueError(f'x must hold B*N values (N = {graph.N})')
+    if out is None:
+        out = ((torch.empty(B * graph.V, 1, dtype=x.dtype, device=x.device),
+                torch.empty(B * graph.V, 1, dtype=x.dtype, device=x.device))
+               + tuple(torch.empty(B, dtype=torch.int32, device=x.device) for _ in range(4)))
+    if len(out) != 6 or out[0] is None:
+        raise ValueError('out must be (ehat, llr, iters_used, status, leg, nsol); only ehat is '
+                         'required')
+    _require_gpu(*out)
+    for t in out[:2]:
+        if t is not None and (t.dtype != x.dtype or t.numel() != B * graph.V
+                              or not t.is_contiguous()):
+            raise ValueError(f'ehat / llr must be contiguous {x.dtype} [{B * graph.V}]')
+    for t in out[2:]:
+        if t is not None and (t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
+            raise ValueError(f'iters_used / status / leg / nsol must be contiguous int32 [{B}]')
+    _relay_impl(graph, x, gammas, iters0, iters_leg, stop_after, alpha, beta, *out)
+    return tuple(out)
+
+
+def _relay_impl(graph, x, gammas, iters0, iters_leg, stop_after, alpha, beta, ehat, llr, iters_used,
+                status, leg, nsol):
+    """gnnd::relay / gnnd::relay_out implementation (gnndecode.library)."""
+    _lib.call('gnnd_relay', graph.handle, dtype_code(x.dtype), _ptr(x), _ptr(gammas),
+              gammas.shape[0], iters0, iters_leg, stop_after, alpha, beta, _ptr(ehat), _ptr(llr),
+              _ptr(iters_used), _ptr(status), _ptr(leg), _ptr(nsol), x.numel() // graph.N,
+              current_stream(x.device))
+
+
+def relay_host(H, x, gammas, iters0, iters_leg=None, stop_after=1, alpha=0.75, beta=0.0):
+    """The host mirror of relay (gnnd_relay_host): numpy in, numpy out, no device.  H [V, C],
+    x [B*N] float32 or float64, gammas [legs, V] (cast to x's dtype) -> (ehat, llr like x's dtype
+    [B*V], iters_used, status, leg, nsol int32 [B])."""
+    import numpy as np
+    from .graph import edge_list
+    H = np.asarray(H)
+    V, C = H.shape
+    x = np.ascontiguousarray(x)
+    if x.dtype not in (np.float32, np.float64):
+        raise TypeError(f'relay_host supports float32/float64, got {x.dtype}')
+    gammas = np.ascontiguousarray(gammas, x.dtype)
+    if gammas.ndim != 2 or gammas.shape[1] != V:
+        raise ValueError(f'gammas must be [legs, V] (V = {V})')
+    legs = gammas.shape[0]
+    iters_leg, alpha, beta = _relay_check_params(iters0, iters_leg, stop_after, alpha, beta, legs)
+    B = x.size // (V + C)
+    if x.size != B * (V + C):
+        raise ValueError(f'x must hold B*N values (N = {V + C})')
+    var, chk = edge_list(H)
+    ehat = np.empty(B * V, x.dtype)
+    llr = np.empty(B * V, x.dtype)
+    ints = [np.empty(B, np.int32) for _ in range(4)]
+    P64, P32 = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
+    _lib.call('gnnd_relay_host', var.ctypes.data_as(P64), chk.ctypes.data_as(P64), var.size, V, C,
+              _lib.F32 if x.dtype == np.float32 else _lib.F64, x.ctypes.data, gammas.ctypes.data,
+              legs, iters0, iters_leg, stop_after, alpha, beta, ehat.ctypes.data, llr.ctypes.data,
+              *(a.ctypes.data_as(P32) for a in ints), B)
+    return (ehat, llr) + tuple(ints)
+
+
+# ---------------------------------------------------------------------------------------
 # gated OSD (gnnd_osd_gated) and the one-call BP+OSD decoder (gnnd_bposd)
 # ---------------------------------------------------------------------------------------
 def osd_gated_workspace(B):

@@ -643,6 +643,68 @@ int gnnd_bposd_layered_host(const int64_t* h_var, const int64_t* h_chk, int64_t 
                             int32_t* h_bp_status, void* h_ehat, int32_t* h_status,
                             int32_t* h_choice, int64_t batch);
 
+/* ---- relay min-sum BP: memory-strength legs that keep the lightest solution ------------------
+ * Min-sum with a per-variable memory term (DMem-BP), run as a chain of "legs": each leg has its own
+ * memory strengths g_v (positive, zero or negative), starts from the posteriors of the leg before,
+ * and ends at its first hard decision that satisfies the syndrome; the solutions are collected and
+ * the lightest is kept.  Adds, one kind of multiply, mins and compares only, in the order fixed
+ * below: every output is bit-reproducible in `dtype` (T = float / double).  The graph, the edge
+ * order, l_v, t_c, a, b, the check step and "`q < 0` is false for -0.0" are gnnd_minsum's.
+ * Inputs beside gnnd_minsum's: d_gammas [legs*V] in dtype, one row per leg, shared by every
+ * codeword; legs >= 1; iters0 >= 1 the iterations of leg 0, iters_leg >= 1 those of every later
+ * leg; stop_after = S >= 1.  Per codeword:
+ *   M_v = l_v;  nsol = 0;  best = none;  total = 0
+ *   for k = 0 .. legs-1:                                  T_k = k == 0 ? iters0 : iters_leg
+ *     g_v = gammas[k*V + v];  c_v = round(1 - g_v)        in T
+ *     Lam_v(M) = (g_v == 0) ? l_v                         selected, not computed: a -0.0 prior stays
+ *              : round(round(c_v * l_v) + round(g_v * M_v))   three roundings, no fused multiply-add
+ *     q_e = Lam_{v(e)}(M)                                 the messages restart, M carries over
+ *     for it = 1 .. T_k:
+ *       total += 1
+ *       check step                                        gnnd_minsum's, on q, giving r_e
+ *       variable step: L_v = ((Lam_v(M) + r_e1) + r_e2) + ...   E(v) ascending, left to right
+ *                      q_e = L_v - r_e;  then M_v = L_v
+ *       h_v = (L_v < 0);  ok = (H^T h == t on every check)
+ *       if ok: w = weight(h);  nsol += 1
+ *              if best is none or w < best.w: best = (L, k, w)    strict: a tie keeps the earlier
+ *              leave leg k
+ *     if nsol >= S: stop
+ *   weight(h): p_j = sum over v = j (mod 64), ascending v, of (h_v ? l_v : +0), starting from +0,
+ *   for j = 0 .. 63; then for s = 32, 16, 8, 4, 2, 1: p_j = p_j + p_{j xor s} (all j at once);
+ *   w = p_0.  The tree is part of the contract, so the device and the mirror agree bit for bit.
+ * Outputs: d_ehat [B*V] in dtype, exactly 0.0 / 1.0, required; d_llr [B*V] in dtype; d_iters,
+ * d_status, d_leg, d_nsol [B] int32; these five may each be NULL.  With a best solution: ehat =
+ * (best.L < 0), llr = best.L, status 0, leg = best.k, nsol the number of solutions collected, iters
+ * = total.  With none: ehat and llr from the last executed iteration, status 1, leg -1, nsol 0,
+ * iters = iters0 + (legs - 1) * iters_leg.  No transcendental appears anywhere in the call.
+ * Guarantees: where d_status[b] == 0, d_ehat of b satisfies the syndrome exactly.  With legs = 1
+ * and an all-zero gammas row, d_llr, d_iters and d_status are the bits of gnnd_minsum with iters =
+ * iters0 and early_stop = 1.  x and gammas must be finite: a non-finite value leaves the outputs of
+ * the codewords it touches unspecified, faults nothing and touches no other codeword's outputs (no
+ * index depends on data).
+ * legs, iters0, iters_leg or stop_after < 1, an iteration total iters0 + (legs - 1) * iters_leg
+ * above 2^31 - 1, alpha or beta outside gnnd_minsum's limits, or a NULL d_x, d_gammas or d_ehat:
+ * GNND_ERR_INVALID_ARG, decided before any device call.  GNND_BF16, a graph with a check of degree
+ * < 2, or a per-codeword LDS tile over 64 KiB: GNND_ERR_UNSUPPORTED, nothing launched.  The tile is
+ * (E + 4 V) values of T, each array rounded up to 16 bytes: the messages, the leg's prior term
+ * round(c_v * l_v), the leg's g_v, M / L, and the best L.  batch 0 returns GNND_OK.  One launch on
+ * `stream`, one wave per codeword, no host sync (capturable).  Feeding the codewords relay leaves
+ * unsolved to gnnd_osd_gated is not part of this entry: gnnd_osd_gated orders the columns by a soft
+ * pred, which relay does not produce.
+ * gnnd_relay_host is the host mirror (plain C++, no device; the graph as the edge list
+ * gnnd_graph_create takes, checked as gnnd_minsum_host checks it): the same definition, the same
+ * bits in every output.                                                                        */
+int gnnd_relay(const gnnd_graph* g, int dtype, const void* d_x, const void* d_gammas,
+               int32_t legs, int32_t iters0, int32_t iters_leg, int32_t stop_after, double alpha,
+               double beta, void* d_ehat, void* d_llr, int32_t* d_iters, int32_t* d_status,
+               int32_t* d_leg, int32_t* d_nsol, int64_t batch, void* stream);
+int gnnd_relay_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                    int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                    const void* h_gammas, int32_t legs, int32_t iters0, int32_t iters_leg,
+                    int32_t stop_after, double alpha, double beta, void* h_ehat, void* h_llr,
+                    int32_t* h_iters, int32_t* h_status, int32_t* h_leg, int32_t* h_nsol,
+                    int64_t batch);
+
 /* Adam (torch.optim.Adam update order, amsgrad/maximize off) on one flat parameter buffer of
  * n values with its two moment buffers; *d_step is the device-resident step count (double,
  * incremented by the call), so a whole training step with the update can be captured in one
