@@ -8,6 +8,7 @@ import functools
 import numpy as np
 
 import minsum_cases as mc
+import minsum_layered_cases as lc
 import osd_cases as oc
 import osd_hi_cases as ohc
 
@@ -91,14 +92,20 @@ def gated_reference(code, B, dtype, base, method, order, gate_name, with_llr):
                    llr_input(code, B, dtype) if with_llr else None, H.shape[0])
 
 
-def bposd_reference(code, B, dtype, pred, base, method, order):
-    """(ehat [B, V] uint8, status, choice, iters_used, bp_status, llr) of gnnd_bposd on
+def bposd_reference(code, B, dtype, pred, base, method, order, schedule='flooding'):
+    """(ehat [B, V] uint8, status, choice, iters_used, bp_status, llr) of gnnd_bposd (of
+    gnnd_bposd_layered with schedule='layered': the BP stage is then the statement of
+    tests/minsum_layered_cases.py) on
     minsum_cases.inputs(code, B, dtype) with bp_params(code).  `pred` [B*V] is the soft
     output the implementation under test returned: it is outside the bit-exact contract (the
     exponential is the library's) and the OSD stage orders its columns by it, so the statement
     takes it as given; the tests hold it to minsum_cases.pred_tolerance separately."""
     H, x = mc.inputs(code, B, dtype)
-    llr, its, st = mc.reference(code, B, dtype, bp_params(code))
+    if schedule == 'layered':
+        llr, its, st = lc.reference(code, B, dtype, bp_params(code))
+    else:
+        assert schedule == 'flooding'
+        llr, its, st = mc.reference(code, B, dtype, bp_params(code))
     full = ohc.ref_batch(H, x, pred, base == 'hard', method, order)
     ehat, status, choice = compose(full, st, pred, llr, H.shape[0])
     return ehat, status, choice, its, st, llr

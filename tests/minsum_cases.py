@@ -8,6 +8,7 @@ import functools
 import numpy as np
 
 import gnndecode as gd
+import synthetic_codes
 
 CODES = ('toric_5', 'toric_7', 'bch_63_45', 'ldpc_648_324')
 # (alpha, beta, iters, early_stop)
@@ -15,11 +16,31 @@ PARAMS = ((0.75, 0.0, 12, 1), (1.0, 0.0, 12, 1), (0.8, 0.1, 10, 1), (0.75, 0.0, 
 TORIC_P = (0.01, 0.04, 0.08, 0.10)
 TORIC_FLIP = 0.04
 SNR_DB = (1.0, 3.0, 5.0, 7.0)
+# added to the seed of a synthetic batch (code, B); searched on the CPU so that the references'
+# own coverage conditions (assert_coverage) hold on both schedules and in both dtypes.  Seed 0
+# serves syn_hub (B = 1, 11) and syn_sq64 (B = 9) without a search
+SYN_SEED = {('syn_wide', 5): 8, ('syn_tall', 9): 4, ('syn_c65', 9): 16}
+# Synthetic graphs too easy for min-sum to fail on at TORIC_FLIP: V = 40 or 64 means two or three
+# flipped bits per codeword, and on 2 700 codewords each (300 seeds, B = 9) neither schedule left
+# one unconverged (syn_tall: every variable sits in 2 to 9 of the 70 checks; syn_sq64: nothing ran
+# past 7 iterations).  Their batches hold status 0 only, and assert_coverage states that; the
+# early exits at different depths remain.  The unconverged path on a synthetic graph is covered
+# by syn_hub, syn_wide and syn_c65.
+SYN_EASY = ('syn_tall', 'syn_sq64')
 
 
 @functools.lru_cache(maxsize=None)
 def code_matrix(code):
+    """H [V, C] of a shipped code or of a synthetic graph of tests/synthetic_codes.py."""
+    if synthetic_codes.is_synthetic(code):
+        return synthetic_codes.matrix(code)
     return gd.codes.get_code(code)
+
+
+def syndrome_style(code):
+    """The codes whose inputs carry a measured syndrome on the check rows: the toric family and
+    the synthetic graphs."""
+    return code.startswith('toric') or synthetic_codes.is_synthetic(code)
 
 
 @functools.lru_cache(maxsize=None)
@@ -94,16 +115,17 @@ def _awgn(rng, B, V, dtype):
 
 @functools.lru_cache(maxsize=None)
 def inputs(code, B, dtype, seed=0):
-    """(H, x [B*N]) in `dtype` ('float32' / 'float64'), read-only.  Toric: priors log((1 - p) / p)
-    with p = TORIC_P[b % 4] on every variable of codeword b, check rows (-1)^(H^T e) of a random
-    error at flip probability TORIC_FLIP (one rate for every prior: each batch then holds early
-    exits at several depths and codewords that never converge).  Classical: _awgn at the variable
-    rows, 0 at the check rows."""
+    """(H, x [B*N]) in `dtype` ('float32' / 'float64'), read-only.  Toric and synthetic
+    (syndrome_style): priors log((1 - p) / p) with p = TORIC_P[b % 4] on every variable of
+    codeword b, check rows (-1)^(H^T e) of a random error at flip probability TORIC_FLIP (one rate
+    for every prior: each batch then holds early exits at several depths and codewords that never
+    converge).  Classical: _awgn at the variable rows, 0 at the check rows.  A synthetic batch
+    adds SYN_SEED[code, B] to the seed."""
     H = code_matrix(code)
     V, C = H.shape
-    rng = np.random.default_rng([seed, B, V, C])
+    rng = np.random.default_rng([seed + SYN_SEED.get((code, B), 0), B, V, C])
     x = np.zeros((B, V + C), np.dtype(dtype))
-    if code.startswith('toric'):
+    if syndrome_style(code):
         for b in range(B):
             p = TORIC_P[b % 4]
             x[b, :V] = np.log((1 - p) / p)
@@ -114,6 +136,26 @@ def inputs(code, B, dtype, seed=0):
     x = x.reshape(-1)
     x.setflags(write=False)
     return H, x
+
+
+def assert_coverage(code, B, dtype, params, its, status):
+    """What a reference batch of B >= 5 must hold, shared with minsum_layered_cases.reference:
+    both statuses (on a SYN_EASY graph: status 0 only, stated here rather than skipped), and
+    under early stop at least two distinct iteration counts with the unconverged codewords at
+    `iters`; without early stop every codeword runs exactly `iters` iterations."""
+    alpha, beta, iters, early_stop = params
+    if B < 5:
+        return
+    tag = (code, B, dtype, params, its.tolist(), status.tolist())
+    if code in SYN_EASY:
+        assert not status.any(), tag
+    else:
+        assert set(status.tolist()) == {0, 1}, tag
+    if early_stop:
+        assert len(set(its.tolist())) >= 2, tag
+        assert (its[status == 1] == iters).all(), tag
+    else:
+        assert (its == iters).all(), tag
 
 
 @functools.lru_cache(maxsize=None)
@@ -131,13 +173,7 @@ def reference(code, B, dtype, params, seed=0):
     llr = np.concatenate([r[0] for r in res])
     its = np.array([r[1] for r in res], np.int32)
     status = np.array([r[2] for r in res], np.int32)
-    if B >= 5:
-        assert set(status.tolist()) == {0, 1}, (code, B, dtype, params, status.tolist())
-        if early_stop:
-            assert len(set(its.tolist())) >= 2, (code, B, dtype, params, its.tolist())
-            assert (its[status == 1] == iters).all()
-        else:
-            assert (its == iters).all()
+    assert_coverage(code, B, dtype, params, its, status)
     for arr in (llr, its, status):
         arr.setflags(write=False)
     return llr, its, status

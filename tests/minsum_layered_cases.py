@@ -126,15 +126,8 @@ def reference(code, B, dtype, params):
     minsum_cases.inputs(code, B, dtype), read-only, with minsum_cases.reference's conditions: a
     batch of B >= 5 holds both statuses, and under early stop at least two distinct iteration
     counts with the unconverged codewords at `iters`, so that no seed hides either path."""
-    alpha, beta, iters, early_stop = params
     llr, its, status = _batch(code, B, dtype, params)
-    if B >= 5:
-        assert set(status.tolist()) == {0, 1}, (code, B, dtype, params, status.tolist())
-        if early_stop:
-            assert len(set(its.tolist())) >= 2, (code, B, dtype, params, its.tolist())
-            assert (its[status == 1] == iters).all()
-        else:
-            assert (its == iters).all()
+    mc.assert_coverage(code, B, dtype, params, its, status)
     for arr in (llr, its, status):
         arr.setflags(write=False)
     return llr, its, status

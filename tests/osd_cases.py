@@ -6,6 +6,7 @@ import functools
 import numpy as np
 
 import gnndecode as gd
+import synthetic_codes
 
 CODES = ('toric_5', 'toric_7', 'bch_63_45', 'ldpc_648_324')
 
@@ -53,11 +54,13 @@ def ref_batch(H, x, p, hard):
 
 @functools.lru_cache(maxsize=None)
 def code_matrix(code):
-    """H [V, C] of a shipped code, or 'bch_dup': BCH(63,45) with check 0 appended again as check
-    18 (C = 19, rank 18)."""
+    """H [V, C] of a shipped code, of a synthetic graph of tests/synthetic_codes.py, or 'bch_dup':
+    BCH(63,45) with check 0 appended again as check 18 (C = 19, rank 18)."""
     if code == 'bch_dup':
         H = gd.codes.bch_63_45()
         return np.concatenate([H, H[:, :1]], axis=1).copy()
+    if synthetic_codes.is_synthetic(code):
+        return synthetic_codes.matrix(code)
     return gd.codes.get_code(code)
 
 
@@ -79,17 +82,23 @@ def soft_outputs(V, B, dtype, rng):
 @functools.lru_cache(maxsize=None)
 def inputs(code, B, dtype, seed=0):
     """(H, x [B*N], p [B*V]) in `dtype` ('float32' / 'float64'), read-only.  Toric check rows carry
-    (-1)^(H^T e) of a random error at flip probability 0.08, classical ones 0; 'bch_dup' carries
-    random +-1 with t_0 != t_18 in even codewords and t_0 == t_18 in odd ones."""
+    (-1)^(H^T e) of a random error at flip probability 0.08, and so do the synthetic graphs',
+    classical ones 0; 'bch_dup' carries random +-1 with t_0 != t_18 in even codewords and
+    t_0 == t_18 in odd ones.  'syn_tall' (more checks than variables, full column rank) has one
+    random target flipped in every odd codeword, which leaves the syndrome outside the image of
+    H^T unless that unit vector happens to lie in it (reference() asserts that some do fail)."""
     H = code_matrix(code)
     V, C = H.shape
     rng = np.random.default_rng([seed, B, V, C, dtype == 'float64'])
     p = soft_outputs(V, B, np.dtype(dtype), rng)
     x = np.empty((B, V + C), np.dtype(dtype))
     x[:, :V] = rng.normal(size=(B, V))
-    if code.startswith('toric'):
+    if code.startswith('toric') or synthetic_codes.is_synthetic(code):
         e = (rng.random((B, V)) < 0.08).astype(np.int64)
         x[:, V:] = 1 - 2 * ((e @ H.astype(np.int64)) % 2)
+        if code == 'syn_tall':
+            for b in range(1, B, 2):
+                x[b, V + rng.integers(C)] *= -1
     elif code == 'bch_dup':
         x[:, V:] = 1 - 2 * rng.integers(0, 2, (B, C))
         x[:, V + 18] = x[:, V]
@@ -106,6 +115,8 @@ def inputs(code, B, dtype, seed=0):
 def reference(code, B, dtype, base, seed=0):
     H, x, p = inputs(code, B, dtype, seed)
     ehat, status = ref_batch(H, x, p, base == 'hard')
+    if code == 'syn_tall' and B >= 2:
+        assert not status[0::2].any() and status[1::2].any(), (B, dtype, base, status.tolist())
     ehat.setflags(write=False)
     status.setflags(write=False)
     return ehat, status
