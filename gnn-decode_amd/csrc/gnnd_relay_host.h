@@ -5,8 +5,13 @@
 // every output: gnnd_minsum_host's check step, c * l + g * M as three roundings (build this header's
 // translation unit with -ffp-contract=off), the variable sum over E(v) in ascending edge order, the
 // weight through the fixed 64-partial tree.
+// Also the mirrors of gnnd_relay_soft (the same loop with the soft output: the MEAN accumulator
+// summed in the variable step in the kernel's order, one multiply by the same host-computed inv,
+// and in fp64 the kernel's exponential, gnnd_exp_f64_device) and of gnnd_relay_osd (that mirror,
+// then gnnd_osd_gated_host).
 #pragma once
 #include "gnnd_minsum_host.h"
+#include "gnnd_osd_host.h"
 
 // legs / iters0 / iters_leg / stop_after / alpha / beta within the contract's limits; the
 // iteration total must fit the int32 d_iters reports
@@ -15,6 +20,21 @@ inline bool gnnd_relay_params_ok(double alpha, double beta, int32_t legs, int32_
     if (legs < 1 || iters0 < 1 || iters_leg < 1 || stop_after < 1) return false;
     if ((int64_t)iters0 + (int64_t)(legs - 1) * iters_leg > 2147483647LL) return false;
     return gnnd_minsum_params_ok(alpha, beta, 1, 1);
+}
+
+inline bool gnnd_relay_soft_ok(int soft) {
+    return soft == GNND_RELAY_SOFT_LAST || soft == GNND_RELAY_SOFT_MEAN;
+}
+
+// the arguments gnnd_relay_osd's two stages refuse with GNND_ERR_INVALID_ARG whatever the graph
+// and the pointers
+inline bool gnnd_relay_osd_params_ok(double alpha, double beta, int32_t legs, int32_t iters0,
+                                     int32_t iters_leg, int32_t stop_after, int soft, int base,
+                                     int method, int32_t order) {
+    if (!gnnd_relay_params_ok(alpha, beta, legs, iters0, iters_leg, stop_after)) return false;
+    if (!gnnd_relay_soft_ok(soft)) return false;
+    if (base != GNND_OSD_BASE_ZERO && base != GNND_OSD_BASE_HARD) return false;
+    return gnnd_osd_order_ok(method, order);
 }
 
 // weight(h) of the contract: 64 partials over v = j (mod 64) in ascending v, then the six-step
@@ -34,13 +54,17 @@ T gnnd_relay_weight(const T* L, const T* l, int V) {
     return p[0];
 }
 
-// every output but ehat may be null
+// every output but ehat may be null.  soft_mode: -1 for gnnd_relay (pred and soft_out unused), else
+// a gnnd_relay_soft_mode: pred is then required and soft_out may be null.  device_exp: the fp64
+// soft output through gnnd_exp_f64_device instead of the host library's exp, as in
+// gnnd_minsum_host_impl
 template <typename T>
 int gnnd_relay_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges, int V,
                          int C, const T* x, const T* gammas, int legs, int iters0, int iters_leg,
                          int stop_after, double alpha, double beta, T* ehat, T* llr,
                          int32_t* iters_out, int32_t* status, int32_t* leg_out, int32_t* nsol_out,
-                         int64_t batch) {
+                         int64_t batch, int soft_mode = -1, T* pred = nullptr,
+                         T* soft_out = nullptr, bool device_exp = false) {
     GnndHostGraph hg;
     const int rc = gnnd_host_graph_build(h_var, h_chk, num_edges, V, C, hg);
     if (rc != GNND_OK) return rc;
@@ -49,10 +73,14 @@ int gnnd_relay_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num
     const T a = (T)alpha, bt = (T)beta;
     const int N = V + C;
     std::vector<T> msg(E), L(V), A(V), best(V);
+    const bool mean = soft_mode == GNND_RELAY_SOFT_MEAN;
+    std::vector<T> acc(mean ? V : 0);
+    const T inv = (T)(1.0 / ((double)iters0 + (double)(legs - 1) * (double)iters_leg));
     for (int64_t b = 0; b < batch; ++b) {
         const T* xv = x + b * N;
         const T* xc = xv + V;
         for (int v = 0; v < V; ++v) L[v] = xv[v];                    // M_v = l_v
+        if (mean) std::fill(acc.begin(), acc.end(), T(0));
         int total = 0, nsol = 0, bestk = -1;
         T bestw = T(0);
         for (int k = 0; k < legs; ++k) {
@@ -98,6 +126,7 @@ int gnnd_relay_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num
                     T s = g[v] == T(0) ? A[v] : lam;
                     for (int e = vptr[v]; e < vptr[v + 1]; ++e) s = s + msg[e];
                     L[v] = s;
+                    if (mean) acc[v] = acc[v] + s;
                     for (int e = vptr[v]; e < vptr[v + 1]; ++e) msg[e] = s - msg[e];
                 }
                 int ok = 1;
@@ -123,6 +152,17 @@ int gnnd_relay_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num
         for (int v = 0; v < V; ++v) {
             ehat[b * V + v] = src[v] < T(0) ? T(1) : T(0);
             if (llr) llr[b * V + v] = src[v];
+            if (soft_mode < 0) continue;
+            T Z = src[v];
+            if (mean && !nsol) {
+                const T Av = acc[v];
+                Z = Av * inv;                                        // one multiply
+            }
+            if (soft_out) soft_out[b * V + v] = Z;
+            if (device_exp && sizeof(T) == sizeof(double))
+                pred[b * V + v] = T(1) / (T(1) + (T)gnnd_exp_f64_device((double)Z));
+            else
+                pred[b * V + v] = T(1) / (T(1) + (T)exp((double)Z));
         }
         if (iters_out) iters_out[b] = total;
         if (status) status[b] = nsol ? 0 : 1;
@@ -155,4 +195,66 @@ inline int gnnd_relay_host_checked(const int64_t* h_var, const int64_t* h_chk, i
                                         (const double*)h_x, (const double*)h_gammas, legs, iters0,
                                         iters_leg, stop_after, alpha, beta, (double*)h_ehat,
                                         (double*)h_llr, h_iters, h_status, h_leg, h_nsol, batch);
+}
+
+// gnnd_relay_soft_host: gnnd_relay_host's checks, then soft and h_pred.  The fp64 exponential is
+// always the device's sequence (device_exp), so h_pred is the device's bits.
+inline int gnnd_relay_soft_host_checked(const int64_t* h_var, const int64_t* h_chk,
+                                        int64_t num_edges, int32_t num_var, int32_t num_chk,
+                                        int dtype, const void* h_x, const void* h_gammas,
+                                        int32_t legs, int32_t iters0, int32_t iters_leg,
+                                        int32_t stop_after, double alpha, double beta, int soft,
+                                        void* h_pred, void* h_soft, void* h_ehat, void* h_llr,
+                                        int32_t* h_iters, int32_t* h_status, int32_t* h_leg,
+                                        int32_t* h_nsol, int64_t batch) {
+    if (!h_var || !h_chk || num_edges <= 0 || num_var <= 0 || num_chk <= 0 || batch < 0)
+        return GNND_ERR_INVALID_ARG;
+    if (!gnnd_relay_params_ok(alpha, beta, legs, iters0, iters_leg, stop_after) ||
+        !gnnd_relay_soft_ok(soft))
+        return GNND_ERR_INVALID_ARG;
+    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
+    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    if (batch == 0) return GNND_OK;
+    if (!h_x || !h_gammas || !h_ehat || !h_pred) return GNND_ERR_INVALID_ARG;
+    if (dtype == GNND_F32)
+        return gnnd_relay_host_impl<float>(h_var, h_chk, num_edges, num_var, num_chk,
+                                           (const float*)h_x, (const float*)h_gammas, legs, iters0,
+                                           iters_leg, stop_after, alpha, beta, (float*)h_ehat,
+                                           (float*)h_llr, h_iters, h_status, h_leg, h_nsol, batch,
+                                           soft, (float*)h_pred, (float*)h_soft, true);
+    return gnnd_relay_host_impl<double>(h_var, h_chk, num_edges, num_var, num_chk,
+                                        (const double*)h_x, (const double*)h_gammas, legs, iters0,
+                                        iters_leg, stop_after, alpha, beta, (double*)h_ehat,
+                                        (double*)h_llr, h_iters, h_status, h_leg, h_nsol, batch,
+                                        soft, (double*)h_pred, (double*)h_soft, true);
+}
+
+// gnnd_relay_osd_host: the soft mirror, then gnnd_osd_gated_host with the relay status as the gate
+inline int gnnd_relay_osd_host_checked(const int64_t* h_var, const int64_t* h_chk,
+                                       int64_t num_edges, int32_t num_var, int32_t num_chk,
+                                       int dtype, const void* h_x, const void* h_gammas,
+                                       int32_t legs, int32_t iters0, int32_t iters_leg,
+                                       int32_t stop_after, double alpha, double beta, int soft,
+                                       int base, int method, int32_t order, void* h_pred,
+                                       void* h_llr, int32_t* h_iters, int32_t* h_relay_status,
+                                       int32_t* h_leg, int32_t* h_nsol, void* h_ehat,
+                                       int32_t* h_status, int32_t* h_choice, int64_t batch) {
+    if (!h_var || !h_chk || num_edges <= 0 || num_var <= 0 || num_chk <= 0 || batch < 0)
+        return GNND_ERR_INVALID_ARG;
+    if (!gnnd_relay_osd_params_ok(alpha, beta, legs, iters0, iters_leg, stop_after, soft, base,
+                                  method, order))
+        return GNND_ERR_INVALID_ARG;
+    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
+    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    if (batch == 0) return GNND_OK;
+    if (!h_x || !h_gammas || !h_pred || !h_llr || !h_relay_status || !h_ehat || !h_status)
+        return GNND_ERR_INVALID_ARG;
+    const int st = gnnd_relay_soft_host_checked(h_var, h_chk, num_edges, num_var, num_chk, dtype,
+                                                h_x, h_gammas, legs, iters0, iters_leg, stop_after,
+                                                alpha, beta, soft, h_pred, nullptr, h_ehat, h_llr,
+                                                h_iters, h_relay_status, h_leg, h_nsol, batch);
+    if (st != GNND_OK) return st;
+    return gnnd_osd_gated_host_checked(h_var, h_chk, num_edges, num_var, num_chk, dtype, h_x,
+                                       h_pred, h_llr, h_relay_status, base, method, order, h_ehat,
+                                       h_status, h_choice, batch);
 }

@@ -37,6 +37,12 @@ a custom op costs more than the 0.47 ms headline kernel, measured r02n):
       lightest solution kept
   gnnd::relay_out(graph_id, x, gammas, iters0, iters_leg, stop_after, alpha, beta, ehat, llr,
       iters_used, status, leg, nsol)                  the same into its outputs (mutates)
+  gnnd::relay_soft(graph_id, x, gammas, iters0, iters_leg, stop_after, alpha, beta, soft)
+      -> (pred, soft, ehat, llr, iters_used, status, leg, nsol)   relay with a soft output ('last' /
+      'mean' posteriors for the unsolved codewords); gnnd::relay_soft_out mutates its eight outputs
+  gnnd::relay_osd(graph_id, x, gammas, iters0, iters_leg, stop_after, alpha, beta, soft, base,
+      method, order) -> (ehat, status, choice, pred, llr, iters_used, relay_status, leg, nsol)
+      relay_soft, then osd_gated on the unsolved codewords; gnnd::relay_osd_out mutates its nine
 
 The single-codeword Tanner graph is a device object owned by libgnnd, not a tensor: ops
 take the integer id that `register_graph` hands out (TannerGraph does this on creation;
@@ -472,4 +478,100 @@ def relay_out(graph_id: int, x: Tensor, gammas: Tensor, iters0: int, iters_leg: 
 @relay_out.register_fake
 def _relay_out_fake(graph_id, x, gammas, iters0, iters_leg, stop_after, alpha, beta, ehat, llr,
                     iters_used, status, leg, nsol):
+    return None
+
+
+# ---------------------------------------------------------------------------------------
+# relay with a soft output, and relay followed by gated OSD
+# ---------------------------------------------------------------------------------------
+@torch.library.custom_op('gnnd::relay_soft', mutates_args=(), device_types='cuda')
+def relay_soft(graph_id: int, x: Tensor, gammas: Tensor, iters0: int, iters_leg: int,
+               stop_after: int, alpha: float, beta: float, soft: str
+               ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from . import ops
+    g = graph_of(graph_id)
+    x = x.contiguous()
+    B = x.numel() // g.N
+    real = tuple(torch.empty(B * g.V, 1, dtype=x.dtype, device=x.device) for _ in range(4))
+    ints = tuple(torch.empty(B, dtype=torch.int32, device=x.device) for _ in range(4))
+    ops._relay_soft_impl(g, x, gammas.contiguous(), iters0, iters_leg, stop_after, alpha, beta,
+                         soft, *real, *ints)
+    return real + ints
+
+
+@relay_soft.register_fake
+def _relay_soft_fake(graph_id, x, gammas, iters0, iters_leg, stop_after, alpha, beta, soft):
+    V, C, N, E = _DIMS[graph_id]
+    B = x.numel() // N
+    return (tuple(x.new_empty(B * V, 1) for _ in range(4))
+            + tuple(x.new_empty(B, dtype=torch.int32) for _ in range(4)))
+
+
+@torch.library.custom_op('gnnd::relay_soft_out',
+                         mutates_args=('pred', 'soft_out', 'ehat', 'llr', 'iters_used', 'status',
+                                       'leg', 'nsol'), device_types='cuda')
+def relay_soft_out(graph_id: int, x: Tensor, gammas: Tensor, iters0: int, iters_leg: int,
+                   stop_after: int, alpha: float, beta: float, soft: str, pred: Tensor,
+                   soft_out: Tensor, ehat: Tensor, llr: Tensor, iters_used: Tensor, status: Tensor,
+                   leg: Tensor, nsol: Tensor) -> None:
+    from . import ops
+    ops._relay_soft_impl(graph_of(graph_id), x.contiguous(), gammas.contiguous(), iters0, iters_leg,
+                         stop_after, alpha, beta, soft, pred, soft_out, ehat, llr, iters_used,
+                         status, leg, nsol)
+
+
+@relay_soft_out.register_fake
+def _relay_soft_out_fake(graph_id, x, gammas, iters0, iters_leg, stop_after, alpha, beta, soft,
+                         pred, soft_out, ehat, llr, iters_used, status, leg, nsol):
+    return None
+
+
+@torch.library.custom_op('gnnd::relay_osd', mutates_args=(), device_types='cuda')
+def relay_osd(graph_id: int, x: Tensor, gammas: Tensor, iters0: int, iters_leg: int,
+              stop_after: int, alpha: float, beta: float, soft: str, base: str, method: str,
+              order: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor,
+                                   Tensor]:
+    from . import ops
+    g = graph_of(graph_id)
+    x = x.contiguous()
+    B = x.numel() // g.N
+    ehat, pred, llr = (torch.empty(B * g.V, 1, dtype=x.dtype, device=x.device) for _ in range(3))
+    status, choice, iters_used, relay_status, leg, nsol = (
+        torch.empty(B, dtype=torch.int32, device=x.device) for _ in range(6))
+    ops._relay_osd_impl(g, x, gammas.contiguous(), iters0, iters_leg, stop_after, alpha, beta, soft,
+                        base, method, order, ehat, status, choice, pred, llr, iters_used,
+                        relay_status, leg, nsol)
+    return ehat, status, choice, pred, llr, iters_used, relay_status, leg, nsol
+
+
+@relay_osd.register_fake
+def _relay_osd_fake(graph_id, x, gammas, iters0, iters_leg, stop_after, alpha, beta, soft, base,
+                    method, order):
+    V, C, N, E = _DIMS[graph_id]
+    B = x.numel() // N
+
+    def ints():
+        return x.new_empty(B, dtype=torch.int32)
+    return (x.new_empty(B * V, 1), ints(), ints(), x.new_empty(B * V, 1), x.new_empty(B * V, 1),
+            ints(), ints(), ints(), ints())
+
+
+@torch.library.custom_op('gnnd::relay_osd_out',
+                         mutates_args=('ehat', 'status', 'choice', 'pred', 'llr', 'iters_used',
+                                       'relay_status', 'leg', 'nsol'), device_types='cuda')
+def relay_osd_out(graph_id: int, x: Tensor, gammas: Tensor, iters0: int, iters_leg: int,
+                  stop_after: int, alpha: float, beta: float, soft: str, base: str, method: str,
+                  order: int, ehat: Tensor, status: Tensor, choice: Tensor, pred: Tensor,
+                  llr: Tensor, iters_used: Tensor, relay_status: Tensor, leg: Tensor,
+                  nsol: Tensor) -> None:
+    from . import ops
+    ops._relay_osd_impl(graph_of(graph_id), x.contiguous(), gammas.contiguous(), iters0, iters_leg,
+                        stop_after, alpha, beta, soft, base, method, order, ehat, status, choice,
+                        pred, llr, iters_used, relay_status, leg, nsol)
+
+
+@relay_osd_out.register_fake
+def _relay_osd_out_fake(graph_id, x, gammas, iters0, iters_leg, stop_after, alpha, beta, soft, base,
+                        method, order, ehat, status, choice, pred, llr, iters_used, relay_status,
+                        leg, nsol):
     return None

@@ -998,6 +998,209 @@ def relay_host(H, x, gammas, iters0, iters_leg=None, stop_after=1, alpha=0.75, b
 
 
 # ---------------------------------------------------------------------------------------
+# relay with a soft output (gnnd_relay_soft) and the one-call relay+OSD decoder (gnnd_relay_osd)
+# ---------------------------------------------------------------------------------------
+def _relay_check_soft(soft):
+    if soft not in _lib.RELAY_SOFT:
+        raise ValueError(f"soft must be 'last' or 'mean', got {soft!r}")
+
+
+def _relay_device_inputs(name, graph, x, gammas):
+    """The checks ops.relay makes on its device inputs -> (x, gammas) contiguous, B."""
+    _require_gpu(x, gammas)
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f'{name} supports float32/float64, got {x.dtype}')
+    if gammas.dtype != x.dtype:
+        raise TypeError(f'gammas must have the dtype of x ({x.dtype}), got {gammas.dtype}')
+    x = x.contiguous()
+    gammas = gammas.contiguous()
+    B = x.numel() // graph.N
+    if x.numel() != B * graph.N:
+        raise ValueError(f'x must hold B*N values (N = {graph.N})')
+    return x, gammas, B
+
+
+def relay_soft(graph, x, gammas, iters0, iters_leg=None, stop_after=1, alpha=0.75, beta=0.0,
+               soft='last', out=None):
+    """relay with a soft output, one HIP launch (gnnd_relay_soft): everything ops.relay returns,
+    bit for bit, plus a soft LLR per variable and its probability, the input osd_gated needs.  For
+    a solved codeword the soft LLR is the kept solution's llr; for an unsolved one it is the last
+    iteration's llr (soft='last') or the mean of the posteriors over every iteration of every leg
+    (soft='mean').  -> (pred, soft, ehat, llr, iters_used, status, leg, nsol): pred [B*V, 1] =
+    1 / (1 + exp(soft)), soft [B*V, 1], the rest as for relay.  soft is bit-reproducible, pred in
+    float64 too (relay_soft_host gives the same bits).  `out` = the eight tensors to write into;
+    each but pred and ehat may be None to skip it (returned as None)."""
+    if gammas.dim() != 2 or gammas.shape[1] != graph.V:
+        raise ValueError(f'gammas must be [legs, V] (V = {graph.V})')
+    legs = gammas.shape[0]
+    iters_leg, alpha, beta = _relay_check_params(iters0, iters_leg, stop_after, alpha, beta, legs)
+    _relay_check_soft(soft)
+    if torch.compiler.is_compiling():
+        if out is None:
+            return torch.ops.gnnd.relay_soft(graph.gid, x, gammas, iters0, iters_leg, stop_after,
+                                             alpha, beta, soft)
+        if len(out) != 8 or any(o is None for o in out):
+            raise ValueError('traced relay_soft needs all eight out tensors')
+        torch.ops.gnnd.relay_soft_out(graph.gid, x, gammas, iters0, iters_leg, stop_after, alpha,
+                                      beta, soft, *out)
+        return out
+    x, gammas, B = _relay_device_inputs('relay_soft', graph, x, gammas)
+    if out is None:
+        out = (tuple(torch.empty(B * graph.V, 1, dtype=x.dtype, device=x.device) for _ in range(4))
+               + tuple(torch.empty(B, dtype=torch.int32, device=x.device) for _ in range(4)))
+    if len(out) != 8 or out[0] is None or out[2] is None:
+        raise ValueError('out must be (pred, soft, ehat, llr, iters_used, status, leg, nsol); only '
+                         'pred and ehat are required')
+    _require_gpu(*out)
+    for t in out[:4]:
+        if t is not None and (t.dtype != x.dtype or t.numel() != B * graph.V
+                              or not t.is_contiguous()):
+            raise ValueError(f'pred / soft / ehat / llr must be contiguous {x.dtype} '
+                             f'[{B * graph.V}]')
+    for t in out[4:]:
+        if t is not None and (t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
+            raise ValueError(f'iters_used / status / leg / nsol must be contiguous int32 [{B}]')
+    _relay_soft_impl(graph, x, gammas, iters0, iters_leg, stop_after, alpha, beta, soft, *out)
+    return tuple(out)
+
+
+def _relay_soft_impl(graph, x, gammas, iters0, iters_leg, stop_after, alpha, beta, soft, pred,
+                     soft_out, ehat, llr, iters_used, status, leg, nsol):
+    """gnnd::relay_soft / gnnd::relay_soft_out implementation (gnndecode.library)."""
+    _lib.call('gnnd_relay_soft', graph.handle, dtype_code(x.dtype), _ptr(x), _ptr(gammas),
+              gammas.shape[0], iters0, iters_leg, stop_after, alpha, beta, _lib.RELAY_SOFT[soft],
+              _ptr(pred), _ptr(soft_out), _ptr(ehat), _ptr(llr), _ptr(iters_used), _ptr(status),
+              _ptr(leg), _ptr(nsol), x.numel() // graph.N, current_stream(x.device))
+
+
+def relay_osd(graph, x, gammas, iters0, iters_leg=None, stop_after=1, alpha=0.75, beta=0.0,
+              soft='last', base='zero', method='cs', order=10, out=None, work=None):
+    """The relay+OSD decoder in one call (gnnd_relay_osd): relay_soft, then osd_gated with the relay
+    status as the gate and the relay llr as the pass-through decision, three launches on the
+    current stream, no host sync.  -> (ehat, status, choice, pred, llr, iters_used, relay_status,
+    leg, nsol): where relay_status is 0 ehat is relay's kept solution, which satisfies the
+    syndrome, and choice is -1; elsewhere ehat / status / choice are osd's on the soft output
+    `soft` selects.  Everything but a float32 pred is bit-reproducible (relay_osd_host gives the
+    same bits).  `out`: the nine tensors to write into; choice, iters_used, leg and nsol may be
+    None to skip them; `work` as for osd_gated."""
+    if gammas.dim() != 2 or gammas.shape[1] != graph.V:
+        raise ValueError(f'gammas must be [legs, V] (V = {graph.V})')
+    legs = gammas.shape[0]
+    iters_leg, alpha, beta = _relay_check_params(iters0, iters_leg, stop_after, alpha, beta, legs)
+    _relay_check_soft(soft)
+    _osd_check_method(base, method, order)
+    if torch.compiler.is_compiling():
+        if out is None:
+            return torch.ops.gnnd.relay_osd(graph.gid, x, gammas, iters0, iters_leg, stop_after,
+                                            alpha, beta, soft, base, method, order)
+        if len(out) != 9 or any(o is None for o in out):
+            raise ValueError('traced relay_osd needs all nine out tensors')
+        torch.ops.gnnd.relay_osd_out(graph.gid, x, gammas, iters0, iters_leg, stop_after, alpha,
+                                     beta, soft, base, method, order, *out)
+        return out
+    x, gammas, B = _relay_device_inputs('relay_osd', graph, x, gammas)
+    if out is None:
+        def real():
+            return torch.empty(B * graph.V, 1, dtype=x.dtype, device=x.device)
+
+        def ints():
+            return torch.empty(B, dtype=torch.int32, device=x.device)
+        out = (real(), ints(), ints(), real(), real(), ints(), ints(), ints(), ints())
+    if len(out) != 9:
+        raise ValueError('out must be (ehat, status, choice, pred, llr, iters_used, relay_status, '
+                         'leg, nsol)')
+    ehat, status, choice, pred, llr, iters_used, relay_status, leg, nsol = out
+    if any(t is None for t in (ehat, status, pred, llr, relay_status)):
+        raise ValueError('only choice, iters_used, leg and nsol may be None in out')
+    _require_gpu(*out)
+    for t in (ehat, pred, llr):
+        if t.dtype != x.dtype or t.numel() != B * graph.V or not t.is_contiguous():
+            raise ValueError(f'ehat / pred / llr must be contiguous {x.dtype} [{B * graph.V}]')
+    for t in (status, choice, iters_used, relay_status, leg, nsol):
+        if t is not None and (t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
+            raise ValueError('status / choice / iters_used / relay_status / leg / nsol must be '
+                             f'contiguous int32 [{B}]')
+    _relay_osd_impl(graph, x, gammas, iters0, iters_leg, stop_after, alpha, beta, soft, base,
+                    method, order, *out, work=work)
+    return tuple(out)
+
+
+def _relay_osd_impl(graph, x, gammas, iters0, iters_leg, stop_after, alpha, beta, soft, base,
+                    method, order, ehat, status, choice, pred, llr, iters_used, relay_status, leg,
+                    nsol, work=None):
+    """gnnd::relay_osd / gnnd::relay_osd_out implementation (gnndecode.library)."""
+    B = x.numel() // graph.N
+    work, nbytes = _gated_work(work, B, x.device)
+    _lib.call('gnnd_relay_osd', graph.handle, dtype_code(x.dtype), _ptr(x), _ptr(gammas),
+              gammas.shape[0], iters0, iters_leg, stop_after, alpha, beta, _lib.RELAY_SOFT[soft],
+              _lib.OSD_BASE[base], _lib.OSD_METHOD[method], order, _ptr(pred), _ptr(llr),
+              _ptr(iters_used), _ptr(relay_status), _ptr(leg), _ptr(nsol), _ptr(ehat),
+              _ptr(status), _ptr(choice), _ptr(work), nbytes, B, current_stream(x.device))
+
+
+def _relay_host_inputs(name, H, x, gammas):
+    """The checks ops.relay_host makes -> (V, C, var, chk, x, gammas, B)."""
+    import numpy as np
+    from .graph import edge_list
+    H = np.asarray(H)
+    V, C = H.shape
+    x = np.ascontiguousarray(x)
+    if x.dtype not in (np.float32, np.float64):
+        raise TypeError(f'{name} supports float32/float64, got {x.dtype}')
+    gammas = np.ascontiguousarray(gammas, x.dtype)
+    if gammas.ndim != 2 or gammas.shape[1] != V:
+        raise ValueError(f'gammas must be [legs, V] (V = {V})')
+    B = x.size // (V + C)
+    if x.size != B * (V + C):
+        raise ValueError(f'x must hold B*N values (N = {V + C})')
+    var, chk = edge_list(H)
+    return V, C, var, chk, x, gammas, B
+
+
+def relay_soft_host(H, x, gammas, iters0, iters_leg=None, stop_after=1, alpha=0.75, beta=0.0,
+                    soft='last'):
+    """The host mirror of relay_soft (gnnd_relay_soft_host): numpy in, numpy out, no device.
+    -> (pred, soft, ehat, llr like x's dtype [B*V], iters_used, status, leg, nsol int32 [B])."""
+    import numpy as np
+    V, C, var, chk, x, gammas, B = _relay_host_inputs('relay_soft_host', H, x, gammas)
+    legs = gammas.shape[0]
+    iters_leg, alpha, beta = _relay_check_params(iters0, iters_leg, stop_after, alpha, beta, legs)
+    _relay_check_soft(soft)
+    real = [np.empty(B * V, x.dtype) for _ in range(4)]
+    ints = [np.empty(B, np.int32) for _ in range(4)]
+    P64, P32 = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
+    _lib.call('gnnd_relay_soft_host', var.ctypes.data_as(P64), chk.ctypes.data_as(P64), var.size,
+              V, C, _lib.F32 if x.dtype == np.float32 else _lib.F64, x.ctypes.data,
+              gammas.ctypes.data, legs, iters0, iters_leg, stop_after, alpha, beta,
+              _lib.RELAY_SOFT[soft], *(a.ctypes.data for a in real),
+              *(a.ctypes.data_as(P32) for a in ints), B)
+    return tuple(real) + tuple(ints)
+
+
+def relay_osd_host(H, x, gammas, iters0, iters_leg=None, stop_after=1, alpha=0.75, beta=0.0,
+                   soft='last', base='zero', method='cs', order=10):
+    """The host mirror of relay_osd (gnnd_relay_osd_host): numpy in, numpy out, no device.
+    -> (ehat, status, choice, pred, llr, iters_used, relay_status, leg, nsol)."""
+    import numpy as np
+    V, C, var, chk, x, gammas, B = _relay_host_inputs('relay_osd_host', H, x, gammas)
+    legs = gammas.shape[0]
+    iters_leg, alpha, beta = _relay_check_params(iters0, iters_leg, stop_after, alpha, beta, legs)
+    _relay_check_soft(soft)
+    _osd_check_method(base, method, order)
+    ehat, pred, llr = (np.empty(B * V, x.dtype) for _ in range(3))
+    status, choice, iters_used, relay_status, leg, nsol = (np.empty(B, np.int32) for _ in range(6))
+    P64, P32 = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
+    _lib.call('gnnd_relay_osd_host', var.ctypes.data_as(P64), chk.ctypes.data_as(P64), var.size, V,
+              C, _lib.F32 if x.dtype == np.float32 else _lib.F64, x.ctypes.data, gammas.ctypes.data,
+              legs, iters0, iters_leg, stop_after, alpha, beta, _lib.RELAY_SOFT[soft],
+              _lib.OSD_BASE[base], _lib.OSD_METHOD[method], order, pred.ctypes.data,
+              llr.ctypes.data, iters_used.ctypes.data_as(P32), relay_status.ctypes.data_as(P32),
+              leg.ctypes.data_as(P32), nsol.ctypes.data_as(P32), ehat.ctypes.data,
+              status.ctypes.data_as(P32), choice.ctypes.data_as(P32), B)
+    return ehat, status, choice, pred, llr, iters_used, relay_status, leg, nsol
+
+
+# ---------------------------------------------------------------------------------------
 # gated OSD (gnnd_osd_gated) and the one-call BP+OSD decoder (gnnd_bposd)
 # ---------------------------------------------------------------------------------------
 def osd_gated_workspace(B):

@@ -689,8 +689,8 @@ int gnnd_bposd_layered_host(const int64_t* h_var, const int64_t* h_chk, int64_t 
  * (E + 4 V) values of T, each array rounded up to 16 bytes: the messages, the leg's prior term
  * round(c_v * l_v), the leg's g_v, M / L, and the best L.  batch 0 returns GNND_OK.  One launch on
  * `stream`, one wave per codeword, no host sync (capturable).  Feeding the codewords relay leaves
- * unsolved to gnnd_osd_gated is not part of this entry: gnnd_osd_gated orders the columns by a soft
- * pred, which relay does not produce.
+ * unsolved to gnnd_osd_gated needs the soft pred that gnnd_osd_gated orders the columns by:
+ * gnnd_relay_soft below produces it, and gnnd_relay_osd is the pairing in one call.
  * gnnd_relay_host is the host mirror (plain C++, no device; the graph as the edge list
  * gnnd_graph_create takes, checked as gnnd_minsum_host checks it): the same definition, the same
  * bits in every output.                                                                        */
@@ -704,6 +704,78 @@ int gnnd_relay_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edge
                     int32_t stop_after, double alpha, double beta, void* h_ehat, void* h_llr,
                     int32_t* h_iters, int32_t* h_status, int32_t* h_leg, int32_t* h_nsol,
                     int64_t batch);
+
+/* ---- relay with a soft output, and the one-call relay+OSD decoder ----------------------------
+ * gnnd_relay_soft is gnnd_relay, word for word: for the same arguments d_ehat, d_llr, d_iters,
+ * d_status, d_leg and d_nsol are the bits gnnd_relay writes.  It adds a soft LLR Z_v per variable,
+ * the one thing gnnd_osd_gated needs from a BP stage, chosen by `soft` for the codewords relay
+ * could not solve: the posteriors of the last iteration (GNND_RELAY_SOFT_LAST, what gnnd_bposd
+ * uses), or their mean over every iteration of every leg (GNND_RELAY_SOFT_MEAN: a chain of legs
+ * with disordered memory strengths oscillates, and the mean remembers where).  Per codeword, in T:
+ *   accumulator (MEAN only)   A_v = +0 before leg 0;  after the variable step of every executed
+ *                             iteration of every leg: A_v = A_v + L_v        (one addition in T)
+ *   scale                     inv = (T)(1.0 / (double)(iters0 + (legs - 1) * iters_leg)), computed
+ *                             once on the host; the device performs no division for it
+ *   status 0 (both modes)     Z_v = best.L_v, the value written to d_llr
+ *   status 1, LAST            Z_v = L_v of the last executed iteration, which is d_llr
+ *   status 1, MEAN            Z_v = round(A_v * inv)                         (one multiply in T);
+ *                             for such a codeword the executed iteration count is exactly the
+ *                             denominator of inv
+ * Outputs beside gnnd_relay's: d_soft [B*V] in dtype = Z_v, may be NULL; d_pred [B*V] in dtype =
+ * 1 / (1 + exp(Z_v)), required.  In GNND_F64 the exponential is gnnd_bposd's fixed sequence, which
+ * the mirror repeats.  d_soft is bit-reproducible in both dtypes; d_pred is bit-reproducible in
+ * GNND_F64 and outside the contract in GNND_F32 (the device's expf), exactly as for gnnd_minsum.
+ * `soft` outside the enum, or a NULL d_pred: GNND_ERR_INVALID_ARG, decided before any device call.
+ * Every other check, refusal, the non-finite rule and the batch-0 rule follow gnnd_relay.  One
+ * launch, one wave per codeword, capturable.  The LDS tile is gnnd_relay's (E + 4 V) values for
+ * LAST and (E + 5 V) for MEAN (the accumulator), each array rounded up to 16 bytes; over 64 KiB:
+ * GNND_ERR_UNSUPPORTED, nothing launched.
+ *
+ * gnnd_relay_osd is gnnd_relay_soft(... soft -> d_pred, no d_soft, d_ehat, d_llr, d_iters,
+ * d_relay_status, d_leg, d_nsol) followed by the unchanged gnnd_osd_gated(d_x, d_pred, d_llr, gate
+ * = d_relay_status, base, method, order -> d_ehat, d_status, d_choice) on the same stream: three
+ * launches, no host sync.  d_pred, d_llr, d_relay_status, d_ehat, d_status and d_work (as for
+ * gnnd_osd_gated) are required; d_iters, d_leg, d_nsol and d_choice may be NULL.
+ * Guarantee: where d_relay_status[b] == 0, d_ehat of b is relay's own kept solution (d_llr < 0),
+ * which satisfies the syndrome exactly, and d_choice[b] = -1; elsewhere d_ehat of b is gnnd_osd's
+ * estimate, which satisfies it wherever d_status[b] == 0.  With legs = 1, an all-zero gammas row
+ * and LAST, every shared output is the bits of gnnd_bposd with iters = iters0 and early_stop = 1.
+ * Every GNND_ERR_INVALID_ARG of either stage is decided before the first device call;
+ * GNND_ERR_UNSUPPORTED is the union of both stages' conditions, with nothing launched; batch 0
+ * returns GNND_OK.
+ * gnnd_relay_soft_host and gnnd_relay_osd_host are the host mirrors (the graph as the edge list
+ * gnnd_relay_host takes): the same accumulation order, the same inv, the same fixed fp64
+ * exponential, then gnnd_osd_gated_host.  In GNND_F64 every output of both is the device's bits;
+ * in GNND_F32 everything but d_pred is, and with it the estimates of the gated codewords under
+ * gnnd_bposd's caveat (pass-through codewords agree bit for bit).                              */
+typedef enum gnnd_relay_soft_mode {
+    GNND_RELAY_SOFT_LAST = 0, GNND_RELAY_SOFT_MEAN = 1
+} gnnd_relay_soft_mode;
+int gnnd_relay_soft(const gnnd_graph* g, int dtype, const void* d_x, const void* d_gammas,
+                    int32_t legs, int32_t iters0, int32_t iters_leg, int32_t stop_after,
+                    double alpha, double beta, int soft, void* d_pred, void* d_soft, void* d_ehat,
+                    void* d_llr, int32_t* d_iters, int32_t* d_status, int32_t* d_leg,
+                    int32_t* d_nsol, int64_t batch, void* stream);
+int gnnd_relay_soft_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                         int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                         const void* h_gammas, int32_t legs, int32_t iters0, int32_t iters_leg,
+                         int32_t stop_after, double alpha, double beta, int soft, void* h_pred,
+                         void* h_soft, void* h_ehat, void* h_llr, int32_t* h_iters,
+                         int32_t* h_status, int32_t* h_leg, int32_t* h_nsol, int64_t batch);
+int gnnd_relay_osd(const gnnd_graph* g, int dtype, const void* d_x, const void* d_gammas,
+                   int32_t legs, int32_t iters0, int32_t iters_leg, int32_t stop_after,
+                   double alpha, double beta, int soft, int base, int method, int32_t order,
+                   void* d_pred, void* d_llr, int32_t* d_iters, int32_t* d_relay_status,
+                   int32_t* d_leg, int32_t* d_nsol, void* d_ehat, int32_t* d_status,
+                   int32_t* d_choice, void* d_work, int64_t work_bytes, int64_t batch,
+                   void* stream);
+int gnnd_relay_osd_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                        int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                        const void* h_gammas, int32_t legs, int32_t iters0, int32_t iters_leg,
+                        int32_t stop_after, double alpha, double beta, int soft, int base,
+                        int method, int32_t order, void* h_pred, void* h_llr, int32_t* h_iters,
+                        int32_t* h_relay_status, int32_t* h_leg, int32_t* h_nsol, void* h_ehat,
+                        int32_t* h_status, int32_t* h_choice, int64_t batch);
 
 /* Adam (torch.optim.Adam update order, amsgrad/maximize off) on one flat parameter buffer of
  * n values with its two moment buffers; *d_step is the device-resident step count (double,
