@@ -19,6 +19,7 @@ FLOW = {'source_to_target': SOURCE_TO_TARGET, 'target_to_source': TARGET_TO_SOUR
 OSD_BASE = {'zero': 0, 'hard': 1}
 OSD_METHOD = {'osd0': 0, 'cs': 1, 'e': 2}
 RELAY_SOFT = {'last': 0, 'mean': 1}
+BPGD_PICK = {'least': 0, 'most': 1}
 VARIANT = {'v24': 0, 'qgnni': 1, 'qbp': 2, 'cgnni': 3, 'cbp': 4, 'nbp': 5, 'v10': 6, 'v30': 7, 'v22': 8}
 
 _c_i64p = ctypes.POINTER(ctypes.c_int64)
@@ -132,6 +133,11 @@ SIGNATURES = {
                                    _i32, _i32, ctypes.c_double, ctypes.c_double, _int, _int, _int,
                                    _i32, _vp, _vp, _c_i32p, _c_i32p, _c_i32p, _c_i32p, _vp, _c_i32p,
                                    _c_i32p, _i64]),
+    'gnnd_bpgd': (_int, [_vp, _int, _vp, ctypes.c_double, ctypes.c_double, _i32, _i32, _i32, _i32,
+                         _int, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'gnnd_bpgd_host': (_int, [_c_i64p, _c_i64p, _i64, _i32, _i32, _int, _vp, ctypes.c_double,
+                              ctypes.c_double, _i32, _i32, _i32, _i32, _int, ctypes.c_double, _vp,
+                              _vp, _vp, _c_i32p, _c_i32p, _c_i32p, _i64]),
     'gnnd_v24_check_mlp_table': (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     'gnnd_adam_step': (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double,
                               ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp]),

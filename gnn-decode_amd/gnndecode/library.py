@@ -43,6 +43,9 @@ a custom op costs more than the 0.47 ms headline kernel, measured r02n):
   gnnd::relay_osd(graph_id, x, gammas, iters0, iters_leg, stop_after, alpha, beta, soft, base,
       method, order) -> (ehat, status, choice, pred, llr, iters_used, relay_status, leg, nsol)
       relay_soft, then osd_gated on the unsolved codewords; gnnd::relay_osd_out mutates its nine
+  gnnd::bpgd(graph_id, x, iters0, iters_round, rounds, per_round, pick, clamp, alpha, beta)
+      -> (ehat, llr, pred, iters_used, status, ndec)   min-sum BP with guided decimation: priors
+      frozen between BP rounds; gnnd::bpgd_out mutates its six outputs
 
 The single-codeword Tanner graph is a device object owned by libgnnd, not a tensor: ops
 take the integer id that `register_graph` hands out (TannerGraph does this on creation;
@@ -574,4 +577,47 @@ def relay_osd_out(graph_id: int, x: Tensor, gammas: Tensor, iters0: int, iters_l
 def _relay_osd_out_fake(graph_id, x, gammas, iters0, iters_leg, stop_after, alpha, beta, soft, base,
                         method, order, ehat, status, choice, pred, llr, iters_used, relay_status,
                         leg, nsol):
+    return None
+
+
+# ---------------------------------------------------------------------------------------
+# min-sum BP with guided decimation
+# ---------------------------------------------------------------------------------------
+@torch.library.custom_op('gnnd::bpgd', mutates_args=(), device_types='cuda')
+def bpgd(graph_id: int, x: Tensor, iters0: int, iters_round: int, rounds: int, per_round: int,
+         pick: str, clamp: float, alpha: float, beta: float
+         ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from . import ops
+    g = graph_of(graph_id)
+    x = x.contiguous()
+    B = x.numel() // g.N
+    real = tuple(torch.empty(B * g.V, 1, dtype=x.dtype, device=x.device) for _ in range(3))
+    ints = tuple(torch.empty(B, dtype=torch.int32, device=x.device) for _ in range(3))
+    ops._bpgd_impl(g, x, iters0, iters_round, rounds, per_round, pick, clamp, alpha, beta, *real,
+                   *ints)
+    return real + ints
+
+
+@bpgd.register_fake
+def _bpgd_fake(graph_id, x, iters0, iters_round, rounds, per_round, pick, clamp, alpha, beta):
+    V, C, N, E = _DIMS[graph_id]
+    B = x.numel() // N
+    return (tuple(x.new_empty(B * V, 1) for _ in range(3))
+            + tuple(x.new_empty(B, dtype=torch.int32) for _ in range(3)))
+
+
+@torch.library.custom_op('gnnd::bpgd_out',
+                         mutates_args=('ehat', 'llr', 'pred', 'iters_used', 'status', 'ndec'),
+                         device_types='cuda')
+def bpgd_out(graph_id: int, x: Tensor, iters0: int, iters_round: int, rounds: int, per_round: int,
+             pick: str, clamp: float, alpha: float, beta: float, ehat: Tensor, llr: Tensor,
+             pred: Tensor, iters_used: Tensor, status: Tensor, ndec: Tensor) -> None:
+    from . import ops
+    ops._bpgd_impl(graph_of(graph_id), x.contiguous(), iters0, iters_round, rounds, per_round, pick,
+                   clamp, alpha, beta, ehat, llr, pred, iters_used, status, ndec)
+
+
+@bpgd_out.register_fake
+def _bpgd_out_fake(graph_id, x, iters0, iters_round, rounds, per_round, pick, clamp, alpha, beta,
+                   ehat, llr, pred, iters_used, status, ndec):
     return None

@@ -1201,6 +1201,112 @@ def relay_osd_host(H, x, gammas, iters0, iters_leg=None, stop_after=1, alpha=0.7
 
 
 # ---------------------------------------------------------------------------------------
+# min-sum BP with guided decimation: freeze bits between BP rounds (gnnd_bpgd)
+# ---------------------------------------------------------------------------------------
+def _bpgd_check_params(iters0, iters_round, rounds, per_round, pick, clamp, alpha, beta):
+    for name, val, lo in (('iters0', iters0, 1), ('iters_round', iters_round, 1),
+                          ('rounds', rounds, 0), ('per_round', per_round, 1)):
+        if not isinstance(val, int) or isinstance(val, bool) or not lo <= val <= 2 ** 31 - 1:
+            raise ValueError(f'{name} must be an integer >= {lo}, got {val!r}')
+    if iters0 + rounds * iters_round > 2 ** 31 - 1:
+        raise ValueError('iters0 + rounds * iters_round must fit an int32')
+    if pick not in _lib.BPGD_PICK:
+        raise ValueError(f"pick must be 'least' or 'most', got {pick!r}")
+    clamp = float(clamp)
+    if not 0.0 < clamp < float('inf'):
+        raise ValueError(f'clamp must be finite and > 0, got {clamp!r}')
+    alpha, beta = _minsum_check_params(1, alpha, beta)
+    return clamp, alpha, beta
+
+
+def bpgd(graph, x, iters0, iters_round, rounds, per_round=1, pick='least', clamp=25.0, alpha=0.75,
+         beta=0.0, out=None):
+    """Min-sum BP with guided decimation, one HIP launch (gnnd_bpgd, defined in include/gnnd.h):
+    iters0 min-sum iterations, then up to `rounds` rounds that freeze the prior of `per_round`
+    undecimated variables at +-clamp (the sign of their current posterior) and run iters_round
+    more iterations from the same messages; pick='least' freezes the least reliable variables
+    (smallest |llr|, the rule that breaks the ties of a degenerate code), pick='most' the most
+    reliable ones.  A codeword stops at its first hard decision that satisfies the syndrome.
+    x [B*N(,1)] as for minsum -> (ehat, llr, pred, iters_used, status, ndec): ehat [B*V, 1] exactly
+    0.0 / 1.0 and llr [B*V, 1] of the last executed iteration, pred [B*V, 1] = 1 / (1 + exp(llr)),
+    iters_used [B] int32, status [B] int32 0 where ehat satisfies the syndrome, ndec [B] int32 the
+    variables frozen.  Everything but a float32 pred is bit-reproducible (bpgd_host gives the same
+    bits); pred, status and llr are what osd_gated takes.  No host sync; `out` = the six tensors to
+    write into, each but ehat may be None to skip it (returned as None)."""
+    clamp, alpha, beta = _bpgd_check_params(iters0, iters_round, rounds, per_round, pick, clamp,
+                                            alpha, beta)
+    if torch.compiler.is_compiling():
+        if out is None:
+            return torch.ops.gnnd.bpgd(graph.gid, x, iters0, iters_round, rounds, per_round, pick,
+                                       clamp, alpha, beta)
+        if len(out) != 6 or any(o is None for o in out):
+            raise ValueError('traced bpgd needs out = (ehat, llr, pred, iters_used, status, ndec)')
+        torch.ops.gnnd.bpgd_out(graph.gid, x, iters0, iters_round, rounds, per_round, pick, clamp,
+                                alpha, beta, *out)
+        return out
+    _require_gpu(x)
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f'bpgd supports float32/float64, got {x.dtype}')
+    x = x.contiguous()
+    B = x.numel() // graph.N
+    if x.numel() != B * graph.N:
+        raise ValueError(f'x must hold B*N values (N = {graph.N})')
+    if out is None:
+        out = (tuple(torch.empty(B * graph.V, 1, dtype=x.dtype, device=x.device) for _ in range(3))
+               + tuple(torch.empty(B, dtype=torch.int32, device=x.device) for _ in range(3)))
+    if len(out) != 6 or out[0] is None:
+        raise ValueError('out must be (ehat, llr, pred, iters_used, status, ndec); only ehat is '
+                         'required')
+    _require_gpu(*out)
+    for t in out[:3]:
+        if t is not None and (t.dtype != x.dtype or t.numel() != B * graph.V
+                              or not t.is_contiguous()):
+            raise ValueError(f'ehat / llr / pred must be contiguous {x.dtype} [{B * graph.V}]')
+    for t in out[3:]:
+        if t is not None and (t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
+            raise ValueError(f'iters_used / status / ndec must be contiguous int32 [{B}]')
+    _bpgd_impl(graph, x, iters0, iters_round, rounds, per_round, pick, clamp, alpha, beta, *out)
+    return tuple(out)
+
+
+def _bpgd_impl(graph, x, iters0, iters_round, rounds, per_round, pick, clamp, alpha, beta, ehat,
+               llr, pred, iters_used, status, ndec):
+    """gnnd::bpgd / gnnd::bpgd_out implementation (gnndecode.library)."""
+    _lib.call('gnnd_bpgd', graph.handle, dtype_code(x.dtype), _ptr(x), alpha, beta, iters0,
+              iters_round, rounds, per_round, _lib.BPGD_PICK[pick], clamp, _ptr(ehat), _ptr(llr),
+              _ptr(pred), _ptr(iters_used), _ptr(status), _ptr(ndec), x.numel() // graph.N,
+              current_stream(x.device))
+
+
+def bpgd_host(H, x, iters0, iters_round, rounds, per_round=1, pick='least', clamp=25.0, alpha=0.75,
+              beta=0.0):
+    """The host mirror of bpgd (gnnd_bpgd_host): numpy in, numpy out, no device.  H [V, C], x [B*N]
+    float32 or float64 -> (ehat, llr, pred like x's dtype [B*V], iters_used, status, ndec int32
+    [B])."""
+    import numpy as np
+    from .graph import edge_list
+    clamp, alpha, beta = _bpgd_check_params(iters0, iters_round, rounds, per_round, pick, clamp,
+                                            alpha, beta)
+    H = np.asarray(H)
+    V, C = H.shape
+    x = np.ascontiguousarray(x)
+    if x.dtype not in (np.float32, np.float64):
+        raise TypeError(f'bpgd_host supports float32/float64, got {x.dtype}')
+    B = x.size // (V + C)
+    if x.size != B * (V + C):
+        raise ValueError(f'x must hold B*N values (N = {V + C})')
+    var, chk = edge_list(H)
+    real = [np.empty(B * V, x.dtype) for _ in range(3)]
+    ints = [np.empty(B, np.int32) for _ in range(3)]
+    P64, P32 = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
+    _lib.call('gnnd_bpgd_host', var.ctypes.data_as(P64), chk.ctypes.data_as(P64), var.size, V, C,
+              _lib.F32 if x.dtype == np.float32 else _lib.F64, x.ctypes.data, alpha, beta, iters0,
+              iters_round, rounds, per_round, _lib.BPGD_PICK[pick], clamp,
+              *(a.ctypes.data for a in real), *(a.ctypes.data_as(P32) for a in ints), B)
+    return tuple(real) + tuple(ints)
+
+
+# ---------------------------------------------------------------------------------------
 # gated OSD (gnnd_osd_gated) and the one-call BP+OSD decoder (gnnd_bposd)
 # ---------------------------------------------------------------------------------------
 def osd_gated_workspace(B):

@@ -777,6 +777,69 @@ int gnnd_relay_osd_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_
                         int32_t* h_relay_status, int32_t* h_leg, int32_t* h_nsol, void* h_ehat,
                         int32_t* h_status, int32_t* h_choice, int64_t batch);
 
+/* ---- min-sum BP with guided decimation: freeze bits between BP rounds -------------------------
+ * BP guided decimation (BPGD), the elimination-free cure for the degeneracy that traps BP on
+ * quantum codes: a few min-sum iterations, then the prior of one (or a few) variables is frozen at
+ * a large LLR of the sign BP currently gives it, and BP goes on from the same messages.  `pick`
+ * chooses which variables: GNND_BPGD_LEAST the least reliable ones (smallest |L_v|: it breaks the
+ * symmetric ties of a degenerate code), GNND_BPGD_MOST the most reliable ones (largest |L_v|: the
+ * published rule for hypergraph-product codes).  Adds, one kind of multiply, mins and compares
+ * only, in the order fixed below.  The graph, the edge order, l_v, t_c, a, b, the check step, the
+ * variable-sum order and "`q < 0` is false for -0.0" are gnnd_minsum's, unchanged; T = float /
+ * double.  iters0 >= 1 the iterations before the first decimation, iters_round >= 1 those after
+ * every decimation, rounds >= 0 the decimation rounds, per_round >= 1 the variables frozen per
+ * round.  Per codeword:
+ *   p_v = l_v;  dec_v = 0;  ndec = 0;  total = 0;  q_e = p_v(e);  c = (T)clamp, rounded once
+ *   for r = 0 .. rounds:                                  T_r = r == 0 ? iters0 : iters_round
+ *     for it = 1 .. T_r:
+ *       total += 1
+ *       check step                                        gnnd_minsum's, on q, giving r_e
+ *       variable step: L_v = ((p_v + r_e1) + r_e2) + ...  E(v) ascending, left to right
+ *                      q_e = L_v - r_e
+ *       h_v = (L_v < 0);  ok = (H^T h == t on every check);  if ok: status 0, stop
+ *     if r == rounds or ndec == V: status 1, stop
+ *     repeat min(per_round, V - ndec) times, every pick reading the same L (this round's last):
+ *       v* = among dec_v == 0 the variable of minimum (LEAST) / maximum (MOST) |L_v|, ties to the
+ *            lowest v: an ascending scan that starts at the first undecimated variable and moves
+ *            on a strict compare only
+ *       p_v* = (L_v* < 0) ? -c : c;  dec_v* = 1;  ndec += 1
+ *     (the messages are not restarted: only p changes, and the next variable step sees it)
+ * Outputs: d_ehat [B*V] in dtype, exactly 0.0 / 1.0 = (L_v < 0) of the last executed iteration,
+ * required; d_llr [B*V] in dtype = that L; d_pred [B*V] in dtype = 1 / (1 + exp(L_v)), in GNND_F64
+ * through gnnd_bposd's fixed exponential (the mirror's bits), in GNND_F32 outside the contract (the
+ * device's expf), as elsewhere; d_iters [B] = total, d_status [B], d_ndec [B] = ndec, int32.  Every
+ * output except d_ehat may be NULL.  d_pred, d_status and d_llr are what gnnd_osd_gated takes, so
+ * the codewords left at status 1 can be handed on as they are.
+ * Guarantees: where d_status[b] == 0, d_ehat of b satisfies the syndrome exactly.  With rounds ==
+ * 0, d_llr, d_iters and d_status are the bits of gnnd_minsum with iters = iters0 and early_stop =
+ * 1.  d_ehat, d_llr, d_iters, d_status and d_ndec are bit-reproducible in both dtypes and equal to
+ * the host mirror's.  x must be finite: a non-finite value leaves the outputs of its codeword
+ * unspecified, faults nothing and touches no other codeword's outputs.  The pick is the one index
+ * in the call that depends on data; by its definition v* is an in-range undecimated variable
+ * whatever the data holds (a NaN never wins a strict compare, and the scan starts at a variable,
+ * not at a sentinel).
+ * iters0 < 1, iters_round < 1, rounds < 0, per_round < 1, an iteration total iters0 + rounds *
+ * iters_round above 2^31 - 1, `pick` outside the enum, clamp not finite or <= 0 (or, in GNND_F32,
+ * above the largest float: c itself must be finite), alpha or beta outside gnnd_minsum's limits,
+ * or a NULL d_x or d_ehat: GNND_ERR_INVALID_ARG, decided before any device call.  GNND_BF16, a
+ * graph with a check of degree < 2, or a per-codeword LDS tile over 64 KiB: GNND_ERR_UNSUPPORTED,
+ * nothing launched.  The tile is (E + 2 V) values of T and V int32, each array rounded up to 16
+ * bytes: the messages, the mutable prior p, L, and the decimated flags.  batch 0 returns GNND_OK.
+ * One launch on `stream`, one wave per codeword, no host sync (capturable).
+ * gnnd_bpgd_host is the host mirror (plain C++, no device; the graph as the edge list
+ * gnnd_graph_create takes, checked as gnnd_minsum_host checks it): the same definition, the same
+ * bits in every output of the contract, and in GNND_F64 in h_pred too.                         */
+typedef enum gnnd_bpgd_pick { GNND_BPGD_LEAST = 0, GNND_BPGD_MOST = 1 } gnnd_bpgd_pick;
+int gnnd_bpgd(const gnnd_graph* g, int dtype, const void* d_x, double alpha, double beta,
+              int32_t iters0, int32_t iters_round, int32_t rounds, int32_t per_round, int pick,
+              double clamp, void* d_ehat, void* d_llr, void* d_pred, int32_t* d_iters,
+              int32_t* d_status, int32_t* d_ndec, int64_t batch, void* stream);
+int gnnd_bpgd_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges, int32_t num_var,
+                   int32_t num_chk, int dtype, const void* h_x, double alpha, double beta,
+                   int32_t iters0, int32_t iters_round, int32_t rounds, int32_t per_round, int pick,
+                   double clamp, void* h_ehat, void* h_llr, void* h_pred, int32_t* h_iters,
+                   int32_t* h_status, int32_t* h_ndec, int64_t batch);
+
 /* Adam (torch.optim.Adam update order, amsgrad/maximize off) on one flat parameter buffer of
  * n values with its two moment buffers; *d_step is the device-resident step count (double,
  * incremented by the call), so a whole training step with the update can be captured in one
