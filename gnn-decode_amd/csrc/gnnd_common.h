@@ -193,6 +193,13 @@ struct gnnd_graph {
     int nlayers, max_layer;   // number of layers, checks in the largest
     int* layer_dev;
     int* layer_of;
+    // Decoding graph of gnnd_uf (include/gnnd.h), kept for a matchable graph only (every variable
+    // of degree 1 or 2); uf_nvert == 0 otherwise.  uf_dev is one device allocation {ends[2 V],
+    // cvirt[C]}: the endpoints a_v < b_v of edge v, and per check the virtual vertex of its
+    // component or -1; uf_ends is the host's [2 V] copy.  Whole graphs only, never a component.
+    int uf_nvert;             // N = C + K
+    int* uf_dev;
+    int* uf_ends;
 };
 constexpr int kMaxComp = 8;
 

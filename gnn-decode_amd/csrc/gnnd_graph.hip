@@ -7,6 +7,7 @@
 // kernels derive batched node/edge ids in closed form.
 #include "gnnd_common.h"
 #include "gnnd_minsum_layered_host.h"   // the layer rule (gnnd_layers_build), shared with the mirror
+#include "gnnd_uf_host.h"               // the decoding-graph rule (gnnd_uf_graph_build), likewise
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -739,6 +740,9 @@ int destroy_graph(gnnd_graph* g) {
     const hipError_t el = hipFree(g->layer_dev);
     if (err == hipSuccess) err = el;
     free(g->layer_of);
+    const hipError_t eu = hipFree(g->uf_dev);
+    if (err == hipSuccess) err = eu;
+    free(g->uf_ends);
     const hipError_t e = hipFree(g->dev);
     if (err == hipSuccess) err = e;
     free(g);
@@ -838,6 +842,26 @@ void split_components(gnnd_graph* g, const int64_t* h_var, const int64_t* h_chk)
     for (int k = 0; k < K; ++k) g->comp[k] = comp[k];
 }
 
+// The decoding graph of gnnd_uf, for a matchable graph: the endpoint and virtual-vertex tables on
+// the device, the endpoints on the host too.  Any other graph keeps uf_nvert == 0 (gnnd_uf and
+// gnnd_graph_matching then refuse it); a failed allocation or copy is an error of the create call.
+int attach_matching(gnnd_graph* g, const int64_t* h_var, const int64_t* h_chk) {
+    const int V = g->view.V, C = g->view.C;
+    GnndUfGraph ug;
+    if (gnnd_uf_graph_build(h_var, h_chk, g->view.E, V, C, ug) != GNND_OK) return GNND_OK;
+    std::vector<int> tab(ug.ends);
+    tab.insert(tab.end(), ug.cvirt.begin(), ug.cvirt.end());
+    g->uf_ends = (int*)malloc(sizeof(int) * 2 * (size_t)V);
+    if (!g->uf_ends) return GNND_ERR_ALLOC;
+    memcpy(g->uf_ends, ug.ends.data(), sizeof(int) * 2 * (size_t)V);
+    hipError_t err = hipMalloc((void**)&g->uf_dev, sizeof(int) * tab.size());
+    if (err != hipSuccess) { g->uf_dev = nullptr; set_hip_error(err); return GNND_ERR_ALLOC; }
+    err = hipMemcpy(g->uf_dev, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice);
+    if (err != hipSuccess) return set_hip_error(err);
+    g->uf_nvert = ug.N;
+    return GNND_OK;
+}
+
 }  // namespace
 
 extern "C" int gnnd_graph_create(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
@@ -846,6 +870,12 @@ extern "C" int gnnd_graph_create(const int64_t* h_var, const int64_t* h_chk, int
     const int rc = create_single(h_var, h_chk, num_edges, V, C, out);
     if (rc != GNND_OK) return rc;
     split_components(*out, h_var, h_chk);
+    const int mrc = attach_matching(*out, h_var, h_chk);
+    if (mrc != GNND_OK) {
+        destroy_graph(*out);
+        *out = nullptr;
+        return mrc;
+    }
     return GNND_OK;
 }
 
@@ -874,6 +904,21 @@ extern "C" int gnnd_graph_layers_host(const int64_t* h_var, const int64_t* h_chk
                                       int32_t* h_layer_of_check) {
     return gnnd_graph_layers_host_checked(h_var, h_chk, num_edges, V, C, h_nlayers,
                                           h_layer_of_check);
+}
+
+extern "C" int gnnd_graph_matching(const gnnd_graph* g, int32_t* h_nvert, int32_t* h_endpoints) {
+    if (!g || !h_nvert) return GNND_ERR_INVALID_ARG;
+    if (g->uf_nvert == 0) return GNND_ERR_UNSUPPORTED;
+    *h_nvert = g->uf_nvert;
+    if (h_endpoints)
+        for (int i = 0; i < 2 * g->view.V; ++i) h_endpoints[i] = g->uf_ends[i];
+    return GNND_OK;
+}
+
+extern "C" int gnnd_graph_matching_host(const int64_t* h_var, const int64_t* h_chk,
+                                        int64_t num_edges, int32_t V, int32_t C, int32_t* h_nvert,
+                                        int32_t* h_endpoints) {
+    return gnnd_graph_matching_host_checked(h_var, h_chk, num_edges, V, C, h_nvert, h_endpoints);
 }
 
 extern "C" int gnnd_graph_set_split(gnnd_graph* g, int32_t enable) {

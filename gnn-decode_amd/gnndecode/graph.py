@@ -72,6 +72,17 @@ class TannerGraph:
                   layer.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
         return layer
 
+    def matching(self):
+        """(N, endpoints int32 [V, 2]): the decoding graph of the union-find decoder
+        (gnnd_graph_matching; ops.uf): vertices 0 .. C-1 the checks and C .. N-1 one virtual vertex
+        per component with a degree-1 variable; variable v is the edge endpoints[v, 0] <
+        endpoints[v, 1].  A graph that is not matchable raises GnndError (GNND_ERR_UNSUPPORTED)."""
+        n = ctypes.c_int32()
+        ends = np.empty((self.V, 2), np.int32)
+        _lib.call('gnnd_graph_matching', self._handle, ctypes.byref(n),
+                  ends.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+        return int(n.value), ends
+
     def set_split(self, enable):
         """Use (default) or bypass the component split for this graph (A/B and tests)."""
         _lib.call('gnnd_graph_set_split', self._handle, int(bool(enable)))

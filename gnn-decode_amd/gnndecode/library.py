@@ -46,6 +46,9 @@ a custom op costs more than the 0.47 ms headline kernel, measured r02n):
   gnnd::bpgd(graph_id, x, iters0, iters_round, rounds, per_round, pick, clamp, alpha, beta)
       -> (ehat, llr, pred, iters_used, status, ndec)   min-sum BP with guided decimation: priors
       frozen between BP rounds; gnnd::bpgd_out mutates its six outputs
+  gnnd::uf(graph_id, x, gate?) -> (ehat, rounds, status, nfull)   the union-find decoder of a
+      matchable graph; rows a gate skips come back as zeros.  gnnd::uf_out(graph_id, x, gate?,
+      ehat, rounds, status, nfull) mutates its four outputs and leaves the skipped rows as they were
 
 The single-codeword Tanner graph is a device object owned by libgnnd, not a tensor: ops
 take the integer id that `register_graph` hands out (TannerGraph does this on creation;
@@ -620,4 +623,41 @@ def bpgd_out(graph_id: int, x: Tensor, iters0: int, iters_round: int, rounds: in
 @bpgd_out.register_fake
 def _bpgd_out_fake(graph_id, x, iters0, iters_round, rounds, per_round, pick, clamp, alpha, beta,
                    ehat, llr, pred, iters_used, status, ndec):
+    return None
+
+
+# ---------------------------------------------------------------------------------------
+# union-find decoding of a matchable code
+# ---------------------------------------------------------------------------------------
+@torch.library.custom_op('gnnd::uf', mutates_args=(), device_types='cuda')
+def uf(graph_id: int, x: Tensor, gate: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    from . import ops
+    g = graph_of(graph_id)
+    x = x.contiguous()
+    B = x.numel() // g.N
+    # zeros, not empty: the rows a gate skips are not written
+    ehat = torch.zeros(B * g.V, 1, dtype=x.dtype, device=x.device)
+    ints = tuple(torch.zeros(B, dtype=torch.int32, device=x.device) for _ in range(3))
+    ops._uf_impl(g, x, None if gate is None else gate.contiguous(), ehat, *ints)
+    return (ehat,) + ints
+
+
+@uf.register_fake
+def _uf_fake(graph_id, x, gate):
+    V, C, N, E = _DIMS[graph_id]
+    B = x.numel() // N
+    return (x.new_empty(B * V, 1),) + tuple(x.new_empty(B, dtype=torch.int32) for _ in range(3))
+
+
+@torch.library.custom_op('gnnd::uf_out', mutates_args=('ehat', 'rounds', 'status', 'nfull'),
+                         device_types='cuda')
+def uf_out(graph_id: int, x: Tensor, gate: Optional[Tensor], ehat: Tensor, rounds: Tensor,
+           status: Tensor, nfull: Tensor) -> None:
+    from . import ops
+    ops._uf_impl(graph_of(graph_id), x.contiguous(), None if gate is None else gate.contiguous(),
+                 ehat, rounds, status, nfull)
+
+
+@uf_out.register_fake
+def _uf_out_fake(graph_id, x, gate, ehat, rounds, status, nfull):
     return None

@@ -1307,6 +1307,102 @@ def bpgd_host(H, x, iters0, iters_round, rounds, per_round=1, pick='least', clam
 
 
 # ---------------------------------------------------------------------------------------
+# union-find decoding of a matchable code: grow, merge, peel (gnnd_uf)
+# ---------------------------------------------------------------------------------------
+def uf(graph, x, gate=None, out=None):
+    """The union-find decoder, one HIP launch (gnnd_uf, defined in include/gnnd.h): clusters grow
+    around the defects of the syndrome in x by half-edges, merge, and a spanning forest of each is
+    peeled.  `graph` must be matchable (every variable of degree 1 or 2, toric_code(L) is); only
+    the signs of x's check rows are read.  x [B*N(,1)] as for minsum -> (ehat, rounds, status,
+    nfull): ehat [B*V, 1] exactly 0.0 / 1.0, which always satisfies the syndrome; rounds [B] int32
+    the growth rounds; status [B] int32, 0 for a decoded codeword; nfull [B] int32 the fully grown
+    edges.  gate [B] int32 (for instance the status of bpgd, relay or minsum): codewords whose gate
+    is 0 are skipped and none of their outputs written, so
+        ops.uf(g, x, gate=status, out=(ehat, None, status, None))
+    finishes exactly the codewords another decoder left unsolved.  Bit-reproducible (uf_host gives
+    the same bits).  No host sync; `out` = the four tensors to write into, each but ehat may be
+    None to skip it (returned as None)."""
+    if torch.compiler.is_compiling():
+        if out is None:
+            return torch.ops.gnnd.uf(graph.gid, x, gate)
+        if len(out) != 4 or any(o is None for o in out):
+            raise ValueError('traced uf needs out = (ehat, rounds, status, nfull)')
+        torch.ops.gnnd.uf_out(graph.gid, x, gate, *out)
+        return out
+    _require_gpu(x, gate)
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f'uf supports float32/float64, got {x.dtype}')
+    x = x.contiguous()
+    B = x.numel() // graph.N
+    if x.numel() != B * graph.N:
+        raise ValueError(f'x must hold B*N values (N = {graph.N})')
+    if gate is not None:
+        if gate.dtype != torch.int32:
+            raise TypeError(f'gate must be int32, got {gate.dtype}')
+        gate = gate.contiguous()
+        if gate.numel() != B:
+            raise ValueError(f'gate must hold B = {B} values')
+    if out is None:
+        out = ((torch.empty(B * graph.V, 1, dtype=x.dtype, device=x.device),)
+               + tuple(torch.empty(B, dtype=torch.int32, device=x.device) for _ in range(3)))
+    if len(out) != 4 or out[0] is None:
+        raise ValueError('out must be (ehat, rounds, status, nfull); only ehat is required')
+    _require_gpu(*out)
+    if out[0].dtype != x.dtype or out[0].numel() != B * graph.V or not out[0].is_contiguous():
+        raise ValueError(f'ehat must be contiguous {x.dtype} [{B * graph.V}]')
+    for t in out[1:]:
+        if t is not None and (t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
+            raise ValueError(f'rounds / status / nfull must be contiguous int32 [{B}]')
+    _uf_impl(graph, x, gate, *out)
+    return tuple(out)
+
+
+def _uf_impl(graph, x, gate, ehat, rounds, status, nfull):
+    """gnnd::uf / gnnd::uf_out implementation (gnndecode.library)."""
+    _lib.call('gnnd_uf', graph.handle, dtype_code(x.dtype), _ptr(x), _ptr(gate), _ptr(ehat),
+              _ptr(rounds), _ptr(status), _ptr(nfull), x.numel() // graph.N,
+              current_stream(x.device))
+
+
+def uf_host(H, x, gate=None):
+    """The host mirror of uf (gnnd_uf_host): numpy in, numpy out, no device.  H [V, C], x [B*N]
+    float32 or float64, gate [B] int32 or None -> (ehat like x's dtype [B*V], rounds, status, nfull
+    int32 [B]).  The rows a gate skips are returned as zeros."""
+    import numpy as np
+    V, C, var, chk, vp, cp = _host_graph(H)
+    x = np.ascontiguousarray(x)
+    if x.dtype not in (np.float32, np.float64):
+        raise TypeError(f'uf_host supports float32/float64, got {x.dtype}')
+    B = x.size // (V + C)
+    if x.size != B * (V + C):
+        raise ValueError(f'x must hold B*N values (N = {V + C})')
+    P32 = ctypes.POINTER(ctypes.c_int32)
+    if gate is not None:
+        gate = np.ascontiguousarray(gate, dtype=np.int32)
+        if gate.size != B:
+            raise ValueError(f'gate must hold B = {B} values')
+    ehat = np.zeros(B * V, x.dtype)
+    ints = [np.zeros(B, np.int32) for _ in range(3)]
+    _lib.call('gnnd_uf_host', vp, cp, var.size, V, C,
+              _lib.F32 if x.dtype == np.float32 else _lib.F64, x.ctypes.data,
+              None if gate is None else gate.ctypes.data_as(P32), ehat.ctypes.data,
+              *(a.ctypes.data_as(P32) for a in ints), B)
+    return (ehat,) + tuple(ints)
+
+
+def matching_host(H):
+    """The decoding graph of H [V, C] on the host (gnnd_graph_matching_host) -> (N, endpoints
+    int32 [V, 2]), as TannerGraph.matching gives it."""
+    import numpy as np
+    V, C, var, chk, vp, cp = _host_graph(H)
+    n = ctypes.c_int32()
+    ends = np.empty((V, 2), np.int32)
+    _lib.call('gnnd_graph_matching_host', vp, cp, var.size, V, C, ctypes.byref(n),
+              ends.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    return int(n.value), ends
+
+
+# ---------------------------------------------------------------------------------------
 # gated OSD (gnnd_osd_gated) and the one-call BP+OSD decoder (gnnd_bposd)
 # ---------------------------------------------------------------------------------------
 def osd_gated_workspace(B):

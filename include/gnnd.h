@@ -840,6 +840,84 @@ int gnnd_bpgd_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges
                    double clamp, void* h_ehat, void* h_llr, void* h_pred, int32_t* h_iters,
                    int32_t* h_status, int32_t* h_ndec, int64_t batch);
 
+/* ---- union-find decoding of a matchable code: grow, merge, peel --------------------------------
+ * The decoder one reaches for first on a toric or surface code: clusters grow around the defects
+ * by half-edges, merge when they meet, and stop once each holds an even number of defects; a
+ * spanning forest of every cluster is then peeled from the leaves.  Integers only, no iteration
+ * count or damping, no elimination; the priors in x are not read.
+ * Graphs.  The Tanner graph must be matchable: every variable of degree 1 or 2 (toric_code(L) is;
+ * one plaquette of each half is left out of H, so a few variables have degree 1).  Its decoding
+ * graph, built once per graph on the host and kept with it:
+ *   vertices  0 .. C-1 the checks; then one virtual vertex for every connected component of the
+ *             Tanner graph that holds a degree-1 variable, the components taken in ascending order
+ *             of their lowest check and numbered C, C+1, ..; K of them, N = C + K.  A virtual
+ *             vertex stands for the check left out of H: its syndrome bit is whatever makes its
+ *             component's parity even.
+ *   edges     variable v is the edge (a_v, b_v), a_v < b_v: its two checks, or its check and its
+ *             component's virtual vertex.  Parallel edges are legal; self-loops cannot occur.
+ * gnnd_graph_matching returns N in *h_nvert and, where h_endpoints [2 V] is not NULL, a_v at 2 v
+ * and b_v at 2 v + 1; gnnd_graph_matching_host is the same rule on the edge list gnnd_graph_create
+ * takes.  A graph that is not matchable: GNND_ERR_UNSUPPORTED from both.
+ * Per codeword b:
+ *   t_c = (x[b (V + C) + V + c] < 0)                      gnnd_osd0's convention; a NaN gives 0
+ *   defect[u] = t_u for u < C; for a virtual u the XOR of t_c over its component's checks
+ *   grow[v] = 0;  label[u] = u;  rounds = 0;  status = 0
+ *   growth round:
+ *     odd[l] = XOR of defect[u] over the vertices with label[u] == l
+ *     if no l is odd: growth ends
+ *     every edge v: grow[v] = min(2, grow[v] + odd[label[a_v]] + odd[label[b_v]]), all edges from
+ *       the same labels: one half-edge from each end that lies in an odd cluster
+ *     if no edge changed: status = 1, growth ends (see below); the round is not counted
+ *     rounds += 1
+ *     labels: those of the connected components over the edges with grow == 2, a component's
+ *       label its highest vertex index (the fixed point of label[u] <- max over full edges)
+ *   forest: over the full edges, depth[u] = the BFS distance from u's label vertex, the root (the
+ *     virtual vertex whenever the cluster holds one: virtual indices are the highest); the parent
+ *     edge of a non-root u = the lowest-numbered full edge (u, w) with depth[w] == depth[u] - 1
+ *   peel: ehat[v] = 1 exactly where v is the parent edge of some u and the defects over u's
+ *     subtree XOR to 1; every other edge 0
+ * Termination.  Every component with a virtual vertex has even parity by construction, so an odd
+ * cluster is never a whole component and always has an edge that is not yet full: some edge grows
+ * in every round and growth ends within 2 V rounds, with no round limit.  A component WITHOUT a
+ * virtual vertex whose syndrome has odd parity has no e with H^T e = t at all; there an odd
+ * cluster ends up as the whole component, a round changes nothing, and the decoder stops with
+ * status 1 (ehat then satisfies every check but that cluster's root).  Nothing else gives status 1.
+ * Outputs: d_ehat [B*V] in dtype, exactly 0.0 / 1.0, required (it feeds gnnd_decision_errors as
+ * is); d_rounds [B] int32 the growth rounds executed; d_status [B] int32, 0 for a decoded
+ * codeword, so the result drops into the places that take a status; d_nfull [B] int32 the number
+ * of full edges when growth ended.  The last three may be NULL.
+ * Gate: d_gate [B] int32 may be NULL.  With a gate, a codeword whose gate is 0 is skipped and none
+ * of its outputs is written: after gnnd_bpgd, gnnd_relay or gnnd_minsum, their d_status as the gate
+ * and their d_ehat (or hard decision) as d_ehat overwrites exactly the unsolved rows.
+ * Guarantees: where d_status[b] == 0, and so for every codeword of a graph whose components all
+ * have a virtual vertex, d_ehat of b satisfies the syndrome exactly, for any x: only the signs of
+ * the check rows are read, a NaN compares false and faults nothing.  All outputs are
+ * bit-reproducible and equal to the host mirror's, in GNND_F32 and GNND_F64 (nothing but the input
+ * and output formats depends on the dtype).  A codeword with zero syndrome returns zero, rounds 0,
+ * nfull 0.
+ * Kernel: one launch on `stream`, one wave per codeword, no host sync (capturable).  The wave's
+ * LDS tile is (V + 4 N) int32, each of the five arrays rounded up to 16 bytes: grow [V], label [N],
+ * defect / subtree parity [N], odd / depth [N], parent edge [N].  No data-dependent index leaves
+ * its array: a label starts as its own vertex and is only ever replaced by another vertex's label;
+ * a depth is 0 at a root, else one more than a neighbour's, and is only compared; a parent is the
+ * index of an edge the parent pass visited and is read only for a vertex of depth >= 1, which has
+ * such an edge.  The debug build checks each of them.
+ * A NULL g, d_x or d_ehat or a dtype outside the enum: GNND_ERR_INVALID_ARG.  GNND_BF16, a graph
+ * that is not matchable (a variable of degree 0 or above 2), or a per-codeword tile over 64 KiB:
+ * GNND_ERR_UNSUPPORTED.  All decided before any device call, nothing launched.  batch 0 returns
+ * GNND_OK.
+ * gnnd_uf_host is the host mirror (plain C++, no device, no tile limit): the same definition, the
+ * same refusals, the same bits in every output.                                                 */
+int gnnd_graph_matching(const gnnd_graph* g, int32_t* h_nvert, int32_t* h_endpoints);
+int gnnd_graph_matching_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                             int32_t num_var, int32_t num_chk, int32_t* h_nvert,
+                             int32_t* h_endpoints);
+int gnnd_uf(const gnnd_graph* g, int dtype, const void* d_x, const int32_t* d_gate, void* d_ehat,
+            int32_t* d_rounds, int32_t* d_status, int32_t* d_nfull, int64_t batch, void* stream);
+int gnnd_uf_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges, int32_t num_var,
+                 int32_t num_chk, int dtype, const void* h_x, const int32_t* h_gate, void* h_ehat,
+                 int32_t* h_rounds, int32_t* h_status, int32_t* h_nfull, int64_t batch);
+
 /* Adam (torch.optim.Adam update order, amsgrad/maximize off) on one flat parameter buffer of
  * n values with its two moment buffers; *d_step is the device-resident step count (double,
  * incremented by the call), so a whole training step with the update can be captured in one
