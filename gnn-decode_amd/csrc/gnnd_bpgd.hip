@@ -5,6 +5,7 @@
 // Built with -ffp-contract=off (Makefile XFLAGS_gnnd_bpgd): a * m - b is two roundings, on the
 // device and in the host mirror alike.
 #include "gnnd_common.h"
+#include "gnnd_wave_tile.h"
 #include "gnnd_bpgd_host.h"
 
 // this translation unit's debug word: gnnd_debug_take_bpgd() (tests/bpgd_debug_worker.py reads it
@@ -12,8 +13,7 @@
 GNND_DEBUG_TU(bpgd)
 
 // ---------------------------------------------------------------------------------------
-// The plan of gnnd_relay.hip: one wave per codeword, a wave-private LDS tile, wave fences only, a
-// grid-stride loop over codewords.  A wave's tile:
+// The wave-private-tile plan and the min-sum steps of gnnd_wave_tile.h.  A wave's tile:
 //   msg[E]   T      q_e and r_e in place
 //   pri[V]   T      the mutable prior p_v: l_v, or +-c once v is decimated
 //   llr[V]   T      L_v of the last variable step, which every pick of a round reads
@@ -29,37 +29,24 @@ GNND_DEBUG_TU(bpgd)
 // the next variable step.  That write is the call's one data-dependent index.
 // Leaving on ok, and the stop rules, are wave-uniform branches.
 // ---------------------------------------------------------------------------------------
-constexpr size_t kBpgdLdsLimit = 64 * 1024;     // dynamic LDS of one workgroup without an opt-in
-
 struct BpgdPlan {
     int off_pri, off_llr, off_dec;      // byte offsets inside one wave's tile (msg at 0)
     int wave_bytes;                     // one wave's tile (16-byte multiple)
     int waves;                          // waves per workgroup (0: the tile does not fit)
 };
 
-static inline size_t bpgd_align16(size_t n) { return (n + 15) & ~(size_t)15; }
-
 static BpgdPlan bpgd_plan(int V, int E, size_t elem) {
     BpgdPlan p;
-    const size_t msg = bpgd_align16((size_t)E * elem), node = bpgd_align16((size_t)V * elem);
-    const size_t dec = bpgd_align16((size_t)V * sizeof(int32_t));
+    const size_t msg = wave_tile_align16((size_t)E * elem);
+    const size_t node = wave_tile_align16((size_t)V * elem);
+    const size_t dec = wave_tile_align16((size_t)V * sizeof(int32_t));
     const size_t bytes = msg + 2 * node + dec;      // E, V <= 65535: far below overflow
     p.off_pri = (int)msg;
     p.off_llr = (int)(msg + node);
     p.off_dec = (int)(msg + 2 * node);
     p.wave_bytes = (int)bytes;
-    p.waves = 0;
-    if (bytes <= kBpgdLdsLimit) {
-        const int fit = (int)(kBpgdLdsLimit / bytes);
-        p.waves = fit < 4 ? fit : 4;
-    }
+    p.waves = wave_tile_waves(bytes);
     return p;
-}
-
-__device__ __forceinline__ void bpgd_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 struct BpgdArgs {
@@ -83,8 +70,7 @@ __global__ void __launch_bounds__(256)
 bpgd_kernel(GraphView g, BpgdPlan pl, BpgdArgs ba, T a, T bt, T cl, const T* __restrict__ x,
             T* __restrict__ ehat, T* __restrict__ llr, T* __restrict__ pred, int64_t B) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int V = g.V, C = g.C, E = g.E, N = g.N;
-    (void)E;                                // read by the debug build's index checks only
+    const int V = g.V, N = g.N;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     char* tile = smem + (size_t)wave * pl.wave_bytes;
     T* s_msg = (T*)tile;
@@ -101,64 +87,26 @@ bpgd_kernel(GraphView g, BpgdPlan pl, BpgdArgs ba, T a, T bt, T cl, const T* __r
             const T l = xv[v];
             s_pri[v] = l;
             s_dec[v] = 0;
-            for (int e = g.var_ptr[v]; e < g.var_ptr[v + 1]; ++e)
-                s_msg[GNND_DIDX(e, E, GNND_DBG_SLOT)] = l;
+            bp_msg_fill(g, s_msg, v, l);
         }
-        bpgd_wave_sync();
+        wave_tile_sync();
         int total = 0, ndec = 0;
         bool ok = false;
         for (int r = 0;; ++r) {
             const int Tr = r == 0 ? ba.iters0 : ba.iters_round;
             for (int it = 0; it < Tr; ++it) {
                 ++total;
-                // ---- check step (gnnd_minsum's) ----
-                for (int c = lane; c < C; c += 64) {
-                    const int i0 = g.chk_ptr[c], i1 = g.chk_ptr[c + 1];
-                    T min1 = (T)INFINITY, min2 = (T)INFINITY;
-                    int arg = -1;
-                    int par = xc[c] < T(0);
-                    for (int i = i0; i < i1; ++i) {
-                        const int e = GNND_DIDX(g.chk_edge[GNND_DIDX(i, E, GNND_DBG_SLOT)], E, GNND_DBG_SLOT);
-                        const T q = s_msg[e];
-                        const T aq = g_abs(q);
-                        par ^= (int)(q < T(0));
-                        if (aq < min1) { min2 = min1; min1 = aq; arg = e; }
-                        else if (aq < min2) min2 = aq;
-                    }
-                    for (int i = i0; i < i1; ++i) {
-                        const int e = GNND_DIDX(g.chk_edge[GNND_DIDX(i, E, GNND_DBG_SLOT)], E, GNND_DBG_SLOT);
-                        const T q = s_msg[e];
-                        const T m = e == arg ? min2 : min1;
-                        const T am = a * m;
-                        const T d = am - bt;                    // -ffp-contract=off: two roundings
-                        const T mag = d > T(0) ? d : T(0);
-                        s_msg[e] = (par ^ (int)(q < T(0))) ? -mag : mag;
-                    }
-                }
-                bpgd_wave_sync();
-                // ---- variable step: L_v = p_v + r_e1 + ..., q_e = L_v - r_e ----
+                bp_check_step(g, s_msg, xc, a, bt, lane);
+                wave_tile_sync();
+                // ---- L_v = p_v + r_e1 + ..., q_e = L_v - r_e ----
                 for (int v = lane; v < V; v += 64) {
                     const int e0 = g.var_ptr[v], e1 = g.var_ptr[v + 1];
-                    T s = s_pri[v];
-                    for (int e = e0; e < e1; ++e) s = s + s_msg[GNND_DIDX(e, E, GNND_DBG_SLOT)];
+                    const T s = bp_var_sum(g, s_msg, e0, e1, s_pri[v]);
                     s_llr[v] = s;
-                    for (int e = e0; e < e1; ++e) {
-                        const int ei = GNND_DIDX(e, E, GNND_DBG_SLOT);
-                        s_msg[ei] = s - s_msg[ei];
-                    }
+                    bp_var_extrinsic(g, s_msg, e0, e1, s);
                 }
-                bpgd_wave_sync();
-                // ---- H^T h == t ? ----
-                int bad = 0;
-                for (int c = lane; c < C; c += 64) {
-                    int par = xc[c] < T(0);
-                    for (int i = g.chk_ptr[c]; i < g.chk_ptr[c + 1]; ++i) {
-                        const int e = GNND_DIDX(g.chk_edge[GNND_DIDX(i, E, GNND_DBG_SLOT)], E, GNND_DBG_SLOT);
-                        const int v = GNND_DIDX((int)(g.edge_vc[e] & 0xffffu), V, GNND_DBG_VAR);
-                        par ^= (int)(s_llr[v] < T(0));
-                    }
-                    bad |= par;
-                }
+                wave_tile_sync();
+                const int bad = bp_syndrome_bad(g, s_llr, xc, lane, 64);
                 ok = __ballot(bad) == 0;
                 if (ok) break;
             }
@@ -191,7 +139,7 @@ bpgd_kernel(GraphView g, BpgdPlan pl, BpgdArgs ba, T a, T bt, T cl, const T* __r
                     s_dec[vs] = 1;
                 }
                 ++ndec;
-                bpgd_wave_sync();           // p and dec visible to the next pick / variable step
+                wave_tile_sync();           // p and dec visible to the next pick / variable step
             }
         }
         // ---- outputs (each lane reads back the L_v it wrote) ----
@@ -206,21 +154,15 @@ bpgd_kernel(GraphView g, BpgdPlan pl, BpgdArgs ba, T a, T bt, T cl, const T* __r
             if (ba.status) ba.status[b] = ok ? 0 : 1;
             if (ba.ndec) ba.ndec[b] = ndec;
         }
-        bpgd_wave_sync();                   // tile reads done before the next codeword's writes
+        wave_tile_sync();                   // tile reads done before the next codeword's writes
     }
-}
-
-static unsigned bpgd_blocks(const BpgdPlan& pl, int64_t B) {
-    const int64_t want = (B + pl.waves - 1) / pl.waves;
-    const int64_t cap = 8192 / pl.waves;                  // 32 waves per CU, grid-stride
-    return (unsigned)(want < cap ? want : cap);
 }
 
 template <typename T, bool MOST>
 static int launch_bpgd(const gnnd_graph* g, const BpgdPlan& pl, const BpgdArgs& ba, const void* x,
                        double alpha, double beta, double clamp, void* ehat, void* llr, void* pred,
                        int64_t B, hipStream_t st) {
-    bpgd_kernel<T, MOST><<<bpgd_blocks(pl, B), 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
+    bpgd_kernel<T, MOST><<<wave_tile_blocks(B, pl.waves, pl.waves), 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
         g->view, pl, ba, (T)alpha, (T)beta, (T)clamp, (const T*)x, (T*)ehat, (T*)llr, (T*)pred, B);
     GNND_LAUNCH_CHECK();
     return GNND_OK;
@@ -231,11 +173,11 @@ extern "C" int gnnd_bpgd(const gnnd_graph* g, int dtype, const void* d_x, double
                          int pick, double clamp, void* d_ehat, void* d_llr, void* d_pred,
                          int32_t* d_iters, int32_t* d_status, int32_t* d_ndec, int64_t batch,
                          void* stream) {
-    if (!g || batch < 0) return GNND_ERR_INVALID_ARG;
-    if (!gnnd_bpgd_params_ok(alpha, beta, iters0, iters_round, rounds, per_round, pick, clamp))
-        return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(
+        g && batch >= 0 &&
+            gnnd_bpgd_params_ok(alpha, beta, iters0, iters_round, rounds, per_round, pick, clamp),
+        dtype);
+    if (rc != GNND_OK) return rc;
     if (!gnnd_bpgd_clamp_fits(dtype, clamp)) return GNND_ERR_INVALID_ARG;
     if (batch == 0) return GNND_OK;
     if (!d_x || !d_ehat) return GNND_ERR_INVALID_ARG;
@@ -244,13 +186,15 @@ extern "C" int gnnd_bpgd(const gnnd_graph* g, int dtype, const void* d_x, double
                                   dtype == GNND_F32 ? sizeof(float) : sizeof(double));
     if (pl.waves == 0) return GNND_ERR_UNSUPPORTED;
     const BpgdArgs ba = {iters0, iters_round, rounds, per_round, d_iters, d_status, d_ndec};
-    hipStream_t st = (hipStream_t)stream;
-#define BPGD_LAUNCH(T, MOST) \
-    launch_bpgd<T, MOST>(g, pl, ba, d_x, alpha, beta, clamp, d_ehat, d_llr, d_pred, batch, st)
-    if (dtype == GNND_F32)
-        return pick == GNND_BPGD_MOST ? BPGD_LAUNCH(float, true) : BPGD_LAUNCH(float, false);
-    return pick == GNND_BPGD_MOST ? BPGD_LAUNCH(double, true) : BPGD_LAUNCH(double, false);
-#undef BPGD_LAUNCH
+    return gnnd_by_dtype(dtype, [&](auto z) {
+        using T = decltype(z);
+        hipStream_t st = (hipStream_t)stream;
+        if (pick == GNND_BPGD_MOST)
+            return launch_bpgd<T, true>(g, pl, ba, d_x, alpha, beta, clamp, d_ehat, d_llr, d_pred,
+                                        batch, st);
+        return launch_bpgd<T, false>(g, pl, ba, d_x, alpha, beta, clamp, d_ehat, d_llr, d_pred,
+                                     batch, st);
+    });
 }
 
 extern "C" int gnnd_bpgd_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,

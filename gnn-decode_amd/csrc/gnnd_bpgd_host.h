@@ -51,56 +51,25 @@ int gnnd_bpgd_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num_
                         int rounds, int per_round, int pick, double clamp, T* ehat, T* llr, T* pred,
                         int32_t* iters_out, int32_t* status, int32_t* ndec_out, int64_t batch) {
     GnndHostGraph hg;
-    const int rc = gnnd_host_graph_build(h_var, h_chk, num_edges, V, C, hg);
+    const int rc = gnnd_host_bp_graph_build(h_var, h_chk, num_edges, V, C, hg);
     if (rc != GNND_OK) return rc;
-    const int E = hg.E;
-    const std::vector<int>&vptr = hg.vptr, &cptr = hg.cptr, &cedge = hg.cedge, &evar = hg.evar;
     const T a = (T)alpha, bt = (T)beta, cl = (T)clamp;
     const int N = V + C;
-    std::vector<T> msg(E), L(V), p(V);
+    std::vector<T> msg(hg.E), L(V), p(V);
     std::vector<unsigned char> dec(V);
     for (int64_t b = 0; b < batch; ++b) {
         const T* xv = x + b * N;
         const T* xc = xv + V;
         for (int v = 0; v < V; ++v) { p[v] = xv[v]; dec[v] = 0; }
-        for (int e = 0; e < E; ++e) msg[e] = p[evar[e]];
+        for (int e = 0; e < hg.E; ++e) msg[e] = p[hg.evar[e]];
         int total = 0, ndec = 0, ok = 0;
         for (int r = 0; ; ++r) {
             const int Tr = r == 0 ? iters0 : iters_round;
             for (int it = 0; it < Tr && !ok; ++it) {
                 ++total;
-                for (int c = 0; c < C; ++c) {
-                    T min1 = std::numeric_limits<T>::infinity(), min2 = min1;
-                    int arg = -1, par = xc[c] < T(0);
-                    for (int i = cptr[c]; i < cptr[c + 1]; ++i) {
-                        const T q = msg[cedge[i]];
-                        const T aq = std::fabs(q);
-                        par ^= (int)(q < T(0));
-                        if (aq < min1) { min2 = min1; min1 = aq; arg = cedge[i]; }
-                        else if (aq < min2) min2 = aq;
-                    }
-                    for (int i = cptr[c]; i < cptr[c + 1]; ++i) {
-                        const int e = cedge[i];
-                        const T q = msg[e];
-                        const T m = e == arg ? min2 : min1;
-                        const T am = a * m;
-                        const T d = am - bt;
-                        const T mag = d > T(0) ? d : T(0);
-                        msg[e] = (par ^ (int)(q < T(0))) ? -mag : mag;
-                    }
-                }
-                for (int v = 0; v < V; ++v) {
-                    T s = p[v];
-                    for (int e = vptr[v]; e < vptr[v + 1]; ++e) s = s + msg[e];
-                    L[v] = s;
-                    for (int e = vptr[v]; e < vptr[v + 1]; ++e) msg[e] = s - msg[e];
-                }
-                ok = 1;
-                for (int c = 0; c < C; ++c) {
-                    int par = xc[c] < T(0);
-                    for (int i = cptr[c]; i < cptr[c + 1]; ++i) par ^= (int)(L[evar[cedge[i]]] < T(0));
-                    if (par) { ok = 0; break; }
-                }
+                gnnd_minsum_check_step(hg, xc, a, bt, msg.data());
+                for (int v = 0; v < V; ++v) L[v] = gnnd_minsum_var_update(hg, v, p[v], msg.data());
+                ok = gnnd_syndrome_ok(hg, xc, L.data());
             }
             if (ok || r == rounds || ndec == V) break;
             const int picks = per_round < V - ndec ? per_round : V - ndec;
@@ -114,11 +83,7 @@ int gnnd_bpgd_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num_
         for (int v = 0; v < V; ++v) {
             ehat[b * V + v] = L[v] < T(0) ? T(1) : T(0);
             if (llr) llr[b * V + v] = L[v];
-            if (!pred) continue;
-            if (sizeof(T) == sizeof(double))
-                pred[b * V + v] = T(1) / (T(1) + (T)gnnd_exp_f64_device((double)L[v]));
-            else
-                pred[b * V + v] = T(1) / (T(1) + (T)exp((double)L[v]));
+            if (pred) pred[b * V + v] = gnnd_soft_output(L[v], /*device_exp=*/true);
         }
         if (iters_out) iters_out[b] = total;
         if (status) status[b] = ok ? 0 : 1;
@@ -133,23 +98,19 @@ inline int gnnd_bpgd_host_checked(const int64_t* h_var, const int64_t* h_chk, in
                                   int32_t rounds, int32_t per_round, int pick, double clamp,
                                   void* h_ehat, void* h_llr, void* h_pred, int32_t* h_iters,
                                   int32_t* h_status, int32_t* h_ndec, int64_t batch) {
-    if (!h_var || !h_chk || num_edges <= 0 || num_var <= 0 || num_chk <= 0 || batch < 0)
-        return GNND_ERR_INVALID_ARG;
-    if (!gnnd_bpgd_params_ok(alpha, beta, iters0, iters_round, rounds, per_round, pick, clamp))
-        return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(
+        gnnd_host_list_ok(h_var, h_chk, num_edges, num_var, num_chk, batch) &&
+            gnnd_bpgd_params_ok(alpha, beta, iters0, iters_round, rounds, per_round, pick, clamp),
+        dtype);
+    if (rc != GNND_OK) return rc;
     if (!gnnd_bpgd_clamp_fits(dtype, clamp)) return GNND_ERR_INVALID_ARG;
     if (batch == 0) return GNND_OK;
     if (!h_x || !h_ehat) return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_F32)
-        return gnnd_bpgd_host_impl<float>(h_var, h_chk, num_edges, num_var, num_chk,
-                                          (const float*)h_x, alpha, beta, iters0, iters_round,
-                                          rounds, per_round, pick, clamp, (float*)h_ehat,
-                                          (float*)h_llr, (float*)h_pred, h_iters, h_status, h_ndec,
-                                          batch);
-    return gnnd_bpgd_host_impl<double>(h_var, h_chk, num_edges, num_var, num_chk,
-                                       (const double*)h_x, alpha, beta, iters0, iters_round, rounds,
-                                       per_round, pick, clamp, (double*)h_ehat, (double*)h_llr,
-                                       (double*)h_pred, h_iters, h_status, h_ndec, batch);
+    return gnnd_by_dtype(dtype, [&](auto z) {
+        using T = decltype(z);
+        return gnnd_bpgd_host_impl<T>(h_var, h_chk, num_edges, num_var, num_chk, (const T*)h_x,
+                                      alpha, beta, iters0, iters_round, rounds, per_round, pick,
+                                      clamp, (T*)h_ehat, (T*)h_llr, (T*)h_pred, h_iters, h_status,
+                                      h_ndec, batch);
+    });
 }

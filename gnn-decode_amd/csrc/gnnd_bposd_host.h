@@ -13,8 +13,7 @@
 inline bool gnnd_bposd_params_ok(double alpha, double beta, int32_t iters, int32_t early_stop,
                                  int base, int method, int32_t order) {
     if (!gnnd_minsum_params_ok(alpha, beta, iters, early_stop)) return false;
-    if (base != GNND_OSD_BASE_ZERO && base != GNND_OSD_BASE_HARD) return false;
-    return gnnd_osd_order_ok(method, order);
+    return gnnd_osd_base_ok(base) && gnnd_osd_order_ok(method, order);
 }
 
 inline int gnnd_bposd_host_checked(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
@@ -23,12 +22,11 @@ inline int gnnd_bposd_host_checked(const int64_t* h_var, const int64_t* h_chk, i
                                    int base, int method, int32_t order, void* h_pred, void* h_llr,
                                    int32_t* h_iters, int32_t* h_bp_status, void* h_ehat,
                                    int32_t* h_status, int32_t* h_choice, int64_t batch) {
-    if (!h_var || !h_chk || num_edges <= 0 || num_var <= 0 || num_chk <= 0 || batch < 0)
-        return GNND_ERR_INVALID_ARG;
-    if (!gnnd_bposd_params_ok(alpha, beta, iters, early_stop, base, method, order))
-        return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(
+        gnnd_host_list_ok(h_var, h_chk, num_edges, num_var, num_chk, batch) &&
+            gnnd_bposd_params_ok(alpha, beta, iters, early_stop, base, method, order),
+        dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!h_x || !h_pred || !h_llr || !h_bp_status || !h_ehat || !h_status)
         return GNND_ERR_INVALID_ARG;

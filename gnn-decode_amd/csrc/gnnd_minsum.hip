@@ -4,6 +4,7 @@
 // Built with -ffp-contract=off (Makefile XFLAGS_gnnd_minsum): a * m - b is two roundings, on the
 // device and in the host mirror alike.
 #include "gnnd_common.h"
+#include "gnnd_wave_tile.h"
 #include "gnnd_minsum_host.h"
 #include "gnnd_bposd_host.h"
 
@@ -13,50 +14,33 @@
 GNND_DEBUG_TU(minsum)
 
 // ---------------------------------------------------------------------------------------
-// One wave per codeword, wave-private LDS, no workgroup barrier (the plan of gnnd_osd.hip).
+// The wave-private-tile plan and the min-sum steps of gnnd_wave_tile.h.
 // A wave's tile: msg[E] (q_e and r_e in place), prior[V] (l_v), llr[V] (L_v), all T.  Per
 // iteration:
-//   check step     lanes own checks lane, lane + 64, ...: one walk over chk_edge keeps min1,
-//                  min2, arg-min and the sign parity, a second walk writes r_e over q_e.  Every
-//                  edge belongs to one check, so the two walks of a lane touch only its own
-//                  edges: no fence between them;
-//   variable step  lanes own variables: l_v + r_e over the var_ptr range in edge order (the
-//                  contract's order; degrees are <= 12 on the shipped codes), then q_e = L_v - r_e
-//                  and L_v into the tile;
-//   convergence    each lane XORs (L_v < 0) over its checks' variables against t_c, one __ballot.
+//   check step     bp_check_step: lanes own checks lane, lane + 64, ...;
+//   variable step  lanes own variables: bp_var_sum from l_v (degrees are <= 12 on the shipped
+//                  codes), L_v into the tile, bp_var_extrinsic;
+//   convergence    bp_syndrome_bad over a lane's checks, one __ballot.
 // The early stop is a wave-uniform branch: a finished codeword costs nothing more and the wave
 // takes its next codeword.  No index depends on the data, so a NaN or an infinity in x stays
 // inside its codeword.
 // ---------------------------------------------------------------------------------------
-constexpr size_t kMinsumLdsLimit = 64 * 1024;   // dynamic LDS of one workgroup without an opt-in
-
 struct MinsumPlan {
     int off_prior, off_llr;   // byte offsets inside one wave's tile (msg at 0)
     int wave_bytes;           // one wave's tile (16-byte multiple)
     int waves;                // waves per workgroup (0: the tile does not fit)
 };
 
-static inline size_t minsum_align16(size_t n) { return (n + 15) & ~(size_t)15; }
-
 static MinsumPlan minsum_plan(int V, int E, size_t elem) {
     MinsumPlan p;
-    const size_t msg = minsum_align16((size_t)E * elem), node = minsum_align16((size_t)V * elem);
+    const size_t msg = wave_tile_align16((size_t)E * elem);
+    const size_t node = wave_tile_align16((size_t)V * elem);
     const size_t bytes = msg + 2 * node;          // E, V <= 65535: far below overflow
     p.off_prior = (int)msg;
     p.off_llr = (int)(msg + node);
     p.wave_bytes = (int)bytes;
-    p.waves = 0;
-    if (bytes <= kMinsumLdsLimit) {
-        const int fit = (int)(kMinsumLdsLimit / bytes);
-        p.waves = fit < 4 ? fit : 4;
-    }
+    p.waves = wave_tile_waves(bytes);
     return p;
-}
-
-__device__ __forceinline__ void minsum_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 template <typename T>
@@ -65,8 +49,7 @@ minsum_kernel(GraphView g, MinsumPlan pl, T a, T bt, int iters, int early_stop,
               const T* __restrict__ x, T* __restrict__ out, T* __restrict__ llr,
               int32_t* __restrict__ iters_out, int32_t* __restrict__ status, int64_t B) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int V = g.V, C = g.C, E = g.E, N = g.N;
-    (void)E;                                // read by the debug build's index checks only
+    const int V = g.V, N = g.N;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     char* tile = smem + (size_t)wave * pl.wave_bytes;
     T* s_msg = (T*)tile;
@@ -81,63 +64,25 @@ minsum_kernel(GraphView g, MinsumPlan pl, T a, T bt, int iters, int early_stop,
         for (int v = lane; v < V; v += 64) {
             const T l = xv[v];
             s_prior[v] = l;
-            for (int e = g.var_ptr[v]; e < g.var_ptr[v + 1]; ++e)
-                s_msg[GNND_DIDX(e, E, GNND_DBG_SLOT)] = l;
+            bp_msg_fill(g, s_msg, v, l);
         }
-        minsum_wave_sync();
+        wave_tile_sync();
         int it = 0;
         bool ok = false;
         while (it < iters) {
             ++it;
-            // ---- check step ----
-            for (int c = lane; c < C; c += 64) {
-                const int i0 = g.chk_ptr[c], i1 = g.chk_ptr[c + 1];
-                T min1 = (T)INFINITY, min2 = (T)INFINITY;
-                int arg = -1;
-                int par = xc[c] < T(0);
-                for (int i = i0; i < i1; ++i) {
-                    const int e = GNND_DIDX(g.chk_edge[GNND_DIDX(i, E, GNND_DBG_SLOT)], E, GNND_DBG_SLOT);
-                    const T q = s_msg[e];
-                    const T aq = g_abs(q);
-                    par ^= (int)(q < T(0));
-                    if (aq < min1) { min2 = min1; min1 = aq; arg = e; }
-                    else if (aq < min2) min2 = aq;
-                }
-                for (int i = i0; i < i1; ++i) {
-                    const int e = GNND_DIDX(g.chk_edge[GNND_DIDX(i, E, GNND_DBG_SLOT)], E, GNND_DBG_SLOT);
-                    const T q = s_msg[e];
-                    const T m = e == arg ? min2 : min1;
-                    const T am = a * m;
-                    const T d = am - bt;                    // -ffp-contract=off: two roundings
-                    const T mag = d > T(0) ? d : T(0);
-                    s_msg[e] = (par ^ (int)(q < T(0))) ? -mag : mag;
-                }
-            }
-            minsum_wave_sync();
-            // ---- variable step ----
+            bp_check_step(g, s_msg, xc, a, bt, lane);
+            wave_tile_sync();
             for (int v = lane; v < V; v += 64) {
                 const int e0 = g.var_ptr[v], e1 = g.var_ptr[v + 1];
-                T s = s_prior[v];
-                for (int e = e0; e < e1; ++e) s = s + s_msg[GNND_DIDX(e, E, GNND_DBG_SLOT)];
+                const T s = bp_var_sum(g, s_msg, e0, e1, s_prior[v]);
                 s_llr[v] = s;
-                for (int e = e0; e < e1; ++e) {
-                    const int ei = GNND_DIDX(e, E, GNND_DBG_SLOT);
-                    s_msg[ei] = s - s_msg[ei];
-                }
+                bp_var_extrinsic(g, s_msg, e0, e1, s);
             }
-            minsum_wave_sync();
+            wave_tile_sync();
             // ---- H^T h == t ? (wanted where it can stop the loop, and after the last iteration) ----
             if (early_stop || it == iters) {
-                int bad = 0;
-                for (int c = lane; c < C; c += 64) {
-                    int par = xc[c] < T(0);
-                    for (int i = g.chk_ptr[c]; i < g.chk_ptr[c + 1]; ++i) {
-                        const int e = GNND_DIDX(g.chk_edge[GNND_DIDX(i, E, GNND_DBG_SLOT)], E, GNND_DBG_SLOT);
-                        const int v = GNND_DIDX((int)(g.edge_vc[e] & 0xffffu), V, GNND_DBG_VAR);
-                        par ^= (int)(s_llr[v] < T(0));
-                    }
-                    bad |= par;
-                }
+                const int bad = bp_syndrome_bad(g, s_llr, xc, lane, 64);
                 ok = __ballot(bad) == 0;
                 if (early_stop && ok) break;
             }
@@ -152,14 +97,8 @@ minsum_kernel(GraphView g, MinsumPlan pl, T a, T bt, int iters, int early_stop,
             if (iters_out) iters_out[b] = it;
             if (status) status[b] = ok ? 0 : 1;
         }
-        minsum_wave_sync();                 // tile reads done before the next codeword's writes
+        wave_tile_sync();                 // tile reads done before the next codeword's writes
     }
-}
-
-static unsigned minsum_blocks(const MinsumPlan& pl, int64_t B) {
-    const int64_t want = (B + pl.waves - 1) / pl.waves;
-    const int64_t cap = 8192 / pl.waves;                  // 32 waves per CU, grid-stride
-    return (unsigned)(want < cap ? want : cap);
 }
 
 template <typename T>
@@ -169,7 +108,7 @@ static int launch_minsum(const gnnd_graph* g, const void* x, double alpha, doubl
     const GraphView& v = g->view;
     const MinsumPlan pl = minsum_plan(v.V, v.E, sizeof(T));
     if (pl.waves == 0) return GNND_ERR_UNSUPPORTED;
-    minsum_kernel<T><<<minsum_blocks(pl, B), 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
+    minsum_kernel<T><<<wave_tile_blocks(B, pl.waves, pl.waves), 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
         v, pl, (T)alpha, (T)beta, iters, early_stop, (const T*)x, (T*)out, (T*)llr, iters_out,
         status, B);
     GNND_LAUNCH_CHECK();
@@ -180,19 +119,16 @@ extern "C" int gnnd_minsum(const gnnd_graph* g, int dtype, const void* d_x, doub
                            double beta, int32_t iters, int32_t early_stop, void* d_out,
                            void* d_llr, int32_t* d_iters, int32_t* d_status, int64_t batch,
                            void* stream) {
-    if (!g || batch < 0) return GNND_ERR_INVALID_ARG;
-    if (!gnnd_minsum_params_ok(alpha, beta, iters, early_stop)) return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(
+        g && batch >= 0 && gnnd_minsum_params_ok(alpha, beta, iters, early_stop), dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!d_x || !d_out) return GNND_ERR_INVALID_ARG;
     if (g->min_dc < 2) return GNND_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == GNND_F32)
-        return launch_minsum<float>(g, d_x, alpha, beta, iters, early_stop, d_out, d_llr, d_iters,
-                                    d_status, batch, st);
-    return launch_minsum<double>(g, d_x, alpha, beta, iters, early_stop, d_out, d_llr, d_iters,
-                                 d_status, batch, st);
+    return gnnd_by_dtype(dtype, [&](auto z) {
+        return launch_minsum<decltype(z)>(g, d_x, alpha, beta, iters, early_stop, d_out, d_llr,
+                                          d_iters, d_status, batch, (hipStream_t)stream);
+    });
 }
 
 extern "C" int gnnd_minsum_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
@@ -216,11 +152,10 @@ extern "C" int gnnd_bposd(const gnnd_graph* g, int dtype, const void* d_x, doubl
                           int32_t* d_bp_status, void* d_ehat, int32_t* d_status,
                           int32_t* d_choice, void* d_work, int64_t work_bytes, int64_t batch,
                           void* stream) {
-    if (!g || batch < 0) return GNND_ERR_INVALID_ARG;
-    if (!gnnd_bposd_params_ok(alpha, beta, iters, early_stop, base, method, order))
-        return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(
+        g && batch >= 0 && gnnd_bposd_params_ok(alpha, beta, iters, early_stop, base, method, order),
+        dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!d_x || !d_pred || !d_llr || !d_bp_status || !d_ehat || !d_status || !d_work)
         return GNND_ERR_INVALID_ARG;

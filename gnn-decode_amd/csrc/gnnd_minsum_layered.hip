@@ -5,6 +5,7 @@
 // -ffp-contract=off (Makefile XFLAGS_gnnd_minsum_layered): a * m - b is two roundings, on the
 // device and in the host mirror alike.
 #include "gnnd_common.h"
+#include "gnnd_wave_tile.h"
 #include "gnnd_minsum_layered_host.h"
 
 // this translation unit's debug word: gnnd_debug_take_minsum_layered() (the pattern of
@@ -14,7 +15,9 @@ GNND_DEBUG_TU(minsum_layered)
 // ---------------------------------------------------------------------------------------
 // The sweep is serial over layers and parallel only inside one, so a codeword gets a sub-wave
 // group of G lanes (a power of two covering the largest layer, 8 <= G <= 64) and a wave holds
-// 64 / G codewords.  Wave-private LDS, no workgroup barrier, no atomics.  A codeword's tile:
+// 64 / G codewords.  Wave-private LDS, no workgroup barrier, no atomics (the fence, the grid rule,
+// the syndrome partial and the magnitude are gnnd_wave_tile.h's; the check walk is this unit's own,
+// for its q = L_v - r_e).  A codeword's tile:
 // r[E] (the check messages), L[V] (the posteriors), all T.  Per iteration, per layer:
 //   each lane owns one check of the layer (slots lane, lane + G, ... where a layer is larger than
 //   G): one walk over its edges gathers q = L_v - r_e and keeps min1, min2, arg-min and the sign
@@ -31,7 +34,6 @@ GNND_DEBUG_TU(minsum_layered)
 // every fence and ballot sits outside the predicated regions.  No index depends on the data, so
 // a NaN or an infinity in x stays inside its codeword even though its neighbours share the wave.
 // ---------------------------------------------------------------------------------------
-constexpr size_t kLayeredLdsLimit = 64 * 1024;   // dynamic LDS of one workgroup without an opt-in
 constexpr size_t kLayeredLdsPerCu = 160 * 1024;
 
 struct LayeredPlan {
@@ -46,8 +48,8 @@ struct LayeredPlan {
 static LayeredPlan layered_plan(const gnnd_graph* g, size_t elem) {
     LayeredPlan p;
     const size_t E = (size_t)g->view.E, V = (size_t)g->view.V;
-    const size_t r_bytes = (E * elem + 15) & ~(size_t)15;
-    size_t bytes = r_bytes + ((V * elem + 15) & ~(size_t)15);   // E, V <= 65535: no overflow
+    const size_t r_bytes = wave_tile_align16(E * elem);
+    size_t bytes = r_bytes + wave_tile_align16(V * elem);       // E, V <= 65535: no overflow
     if (!((bytes >> 4) & 1)) bytes += 16;
     p.off_L = (int)r_bytes;
     p.cw_bytes = (int)bytes;
@@ -55,7 +57,7 @@ static LayeredPlan layered_plan(const gnnd_graph* g, size_t elem) {
     p.max_layer = g->max_layer;
     int G = 8;
     while (G < 64 && G < g->max_layer) G *= 2;
-    while (G < 64 && (size_t)(64 / G) * bytes > kLayeredLdsLimit) G *= 2;   // fewer codewords per wave
+    while (G < 64 && (size_t)(64 / G) * bytes > kWaveTileLdsLimit) G *= 2;   // fewer codewords per wave
     p.G = G;
     p.logG = 0;
     while ((1 << p.logG) < G) ++p.logG;
@@ -64,17 +66,11 @@ static LayeredPlan layered_plan(const gnnd_graph* g, size_t elem) {
     // the workgroup size that keeps most codewords resident on a CU (larger on ties)
     size_t best = 0;
     for (int w = 1; w <= 4; ++w) {
-        if (w * wave_bytes > kLayeredLdsLimit) break;
+        if (w * wave_bytes > kWaveTileLdsLimit) break;
         const size_t resident = (kLayeredLdsPerCu / (w * wave_bytes)) * w;
         if (resident >= best) { best = resident; p.waves = w; }
     }
     return p;
-}
-
-__device__ __forceinline__ void layered_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 template <typename T>
@@ -85,6 +81,7 @@ minsum_layered_kernel(GraphView g, LayeredPlan pl, const int* __restrict__ layer
                       int32_t* __restrict__ iters_out, int32_t* __restrict__ status, int64_t B) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int V = g.V, C = g.C, E = g.E, N = g.N;
+    (void)C;                                        // read by the debug build's index checks only
     const int G = pl.G, K = 64 >> pl.logG;          // K codewords per wave
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int grp = lane >> pl.logG, gl = lane & (G - 1);
@@ -105,7 +102,7 @@ minsum_layered_kernel(GraphView g, LayeredPlan pl, const int* __restrict__ layer
             for (int v = gl; v < V; v += G) s_L[v] = xv[v];
             for (int e = gl; e < E; e += G) s_r[e] = T(0);
         }
-        layered_wave_sync();
+        wave_tile_sync();
         int it = 0;
         bool ok = false, done = !active;
         for (int step = 0; step < iters; ++step) {  // wave-uniform trip count
@@ -133,38 +130,25 @@ minsum_layered_kernel(GraphView g, LayeredPlan pl, const int* __restrict__ layer
                             const int e = GNND_DIDX(g.chk_edge[GNND_DIDX(i, E, GNND_DBG_SLOT)], E, GNND_DBG_SLOT);
                             const int v = GNND_DIDX((int)(g.edge_vc[e] & 0xffffu), V, GNND_DBG_VAR);
                             const T q = s_L[v] - s_r[e];
-                            const T m = e == arg ? min2 : min1;
-                            const T am = a * m;
-                            const T d = am - bt;            // -ffp-contract=off: two roundings
-                            const T mag = d > T(0) ? d : T(0);
-                            const T rn = (par ^ (int)(q < T(0))) ? -mag : mag;
+                            const T rn = bp_signed_mag(a, bt, e == arg ? min2 : min1,
+                                                       par ^ (int)(q < T(0)));
                             s_L[v] = q + rn;
                             s_r[e] = rn;
                         }
                     }
                 }
-                layered_wave_sync();                // between layers, outside the predicate
+                wave_tile_sync();                // between layers, outside the predicate
             }
             // ---- H^T h == t ? (wanted where it can stop the loop, and after the last iteration) ----
             if (early_stop || step == iters - 1) {
                 int bad = 0;
-                if (!done) {
-                    for (int c = gl; c < C; c += G) {
-                        int par = xc[c] < T(0);
-                        for (int i = g.chk_ptr[c]; i < g.chk_ptr[c + 1]; ++i) {
-                            const int e = GNND_DIDX(g.chk_edge[GNND_DIDX(i, E, GNND_DBG_SLOT)], E, GNND_DBG_SLOT);
-                            const int v = GNND_DIDX((int)(g.edge_vc[e] & 0xffffu), V, GNND_DBG_VAR);
-                            par ^= (int)(s_L[v] < T(0));
-                        }
-                        bad |= par;
-                    }
-                }
+                if (!done) bad = bp_syndrome_bad(g, s_L, xc, gl, G);
                 const uint64_t fails = __ballot(bad);       // every lane of the wave takes part
                 if (!done) {
                     ok = (fails & gmask) == 0;
                     if (early_stop && ok) done = true;
                 }
-                layered_wave_sync();                // the L reads above before the next layer's writes
+                wave_tile_sync();                // the L reads above before the next layer's writes
                 if (__ballot(!done) == 0) break;    // wave-uniform: every group has stopped
             }
         }
@@ -180,15 +164,8 @@ minsum_layered_kernel(GraphView g, LayeredPlan pl, const int* __restrict__ layer
                 if (status) status[b] = ok ? 0 : 1;
             }
         }
-        layered_wave_sync();                        // tile reads done before the next codewords' writes
+        wave_tile_sync();                        // tile reads done before the next codewords' writes
     }
-}
-
-static unsigned layered_blocks(const LayeredPlan& pl, int64_t B) {
-    const int64_t per_wg = (int64_t)pl.waves * (64 / pl.G);
-    const int64_t want = (B + per_wg - 1) / per_wg;
-    const int64_t cap = 8192 / pl.waves;                  // 32 waves per CU, grid-stride
-    return (unsigned)(want < cap ? want : cap);
 }
 
 template <typename T>
@@ -198,7 +175,7 @@ static int launch_minsum_layered(const gnnd_graph* g, const void* x, double alph
     const LayeredPlan pl = layered_plan(g, sizeof(T));
     if (pl.waves == 0) return GNND_ERR_UNSUPPORTED;
     const size_t lds = (size_t)pl.waves * (64 / pl.G) * pl.cw_bytes;
-    minsum_layered_kernel<T><<<layered_blocks(pl, B), 64 * pl.waves, lds, st>>>(
+    minsum_layered_kernel<T><<<wave_tile_blocks(B, (int64_t)pl.waves * (64 / pl.G), pl.waves), 64 * pl.waves, lds, st>>>(
         g->view, pl, g->layer_dev, g->layer_dev + pl.nlayers + 1, (T)alpha, (T)beta, iters,
         early_stop, (const T*)x, (T*)out, (T*)llr, iters_out, status, B);
     GNND_LAUNCH_CHECK();
@@ -209,19 +186,17 @@ extern "C" int gnnd_minsum_layered(const gnnd_graph* g, int dtype, const void* d
                                    double beta, int32_t iters, int32_t early_stop, void* d_out,
                                    void* d_llr, int32_t* d_iters, int32_t* d_status,
                                    int64_t batch, void* stream) {
-    if (!g || batch < 0) return GNND_ERR_INVALID_ARG;
-    if (!gnnd_minsum_params_ok(alpha, beta, iters, early_stop)) return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(
+        g && batch >= 0 && gnnd_minsum_params_ok(alpha, beta, iters, early_stop), dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!d_x || !d_out) return GNND_ERR_INVALID_ARG;
     if (g->min_dc < 2) return GNND_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == GNND_F32)
-        return launch_minsum_layered<float>(g, d_x, alpha, beta, iters, early_stop, d_out, d_llr,
-                                            d_iters, d_status, batch, st);
-    return launch_minsum_layered<double>(g, d_x, alpha, beta, iters, early_stop, d_out, d_llr,
-                                         d_iters, d_status, batch, st);
+    return gnnd_by_dtype(dtype, [&](auto z) {
+        return launch_minsum_layered<decltype(z)>(g, d_x, alpha, beta, iters, early_stop, d_out,
+                                                  d_llr, d_iters, d_status, batch,
+                                                  (hipStream_t)stream);
+    });
 }
 
 extern "C" int gnnd_minsum_layered_host(const int64_t* h_var, const int64_t* h_chk,
@@ -236,9 +211,8 @@ extern "C" int gnnd_minsum_layered_host(const int64_t* h_var, const int64_t* h_c
 }
 
 extern "C" int gnnd_minsum_layered_plan(const gnnd_graph* g, int dtype, int32_t* h_plan4) {
-    if (!g || !h_plan4) return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(g && h_plan4, dtype);
+    if (rc != GNND_OK) return rc;
     const LayeredPlan pl = layered_plan(g, dtype == GNND_F32 ? sizeof(float) : sizeof(double));
     if (g->min_dc < 2 || pl.waves == 0) return GNND_ERR_UNSUPPORTED;
     h_plan4[0] = pl.nlayers;
@@ -260,11 +234,10 @@ extern "C" int gnnd_bposd_layered(const gnnd_graph* g, int dtype, const void* d_
                                   int32_t* d_iters, int32_t* d_bp_status, void* d_ehat,
                                   int32_t* d_status, int32_t* d_choice, void* d_work,
                                   int64_t work_bytes, int64_t batch, void* stream) {
-    if (!g || batch < 0) return GNND_ERR_INVALID_ARG;
-    if (!gnnd_bposd_params_ok(alpha, beta, iters, early_stop, base, method, order))
-        return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(
+        g && batch >= 0 && gnnd_bposd_params_ok(alpha, beta, iters, early_stop, base, method, order),
+        dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!d_x || !d_pred || !d_llr || !d_bp_status || !d_ehat || !d_status || !d_work)
         return GNND_ERR_INVALID_ARG;

@@ -42,34 +42,11 @@ inline void gnnd_layers_order(int C, int nl, const std::vector<int>& layer_of,
     for (int c = 0; c < C; ++c) layer_chk[fill[layer_of[c]]++] = c;
 }
 
-// the edge list of gnnd_graph_create -> per-check edge lists; the graph checks of gnnd_minsum_host
-struct GnndLayeredTables {
-    int E = 0;
-    std::vector<int> cptr, cedge, evar, cvar;     // cvar[i] = evar[cedge[i]]
-};
-
-inline int gnnd_layered_tables(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
-                               int V, int C, GnndLayeredTables& t) {
-    if (num_edges > 65535 || V > 65535 || C > 65535) return GNND_ERR_UNSUPPORTED;
-    const int E = (int)num_edges;
-    t.E = E;
-    t.cptr.assign(C + 1, 0);
-    t.cedge.assign(E, 0);
-    t.evar.assign(E, 0);
-    t.cvar.assign(E, 0);
-    for (int e = 0; e < E; ++e) {
-        const int64_t v = h_var[e], c = h_chk[e];
-        if (v < 0 || v >= V || c < 0 || c >= C) return GNND_ERR_GRAPH;
-        if (e > 0 && (v < h_var[e - 1] || (v == h_var[e - 1] && c <= h_chk[e - 1])))
-            return GNND_ERR_GRAPH;                                   // sorted by (v, c), no duplicate
-        t.evar[e] = (int)v;
-        t.cptr[c + 1]++;
-    }
-    for (int c = 0; c < C; ++c) t.cptr[c + 1] += t.cptr[c];
-    std::vector<int> fill(t.cptr.begin(), t.cptr.end() - 1);
-    for (int e = 0; e < E; ++e) t.cedge[fill[h_chk[e]]++] = e;
-    for (int i = 0; i < E; ++i) t.cvar[i] = t.evar[t.cedge[i]];
-    return GNND_OK;
+// cvar[i] = evar[cedge[i]]: the variables check by check, in the order of cedge
+inline std::vector<int> gnnd_host_graph_cvar(const GnndHostGraph& hg) {
+    std::vector<int> cvar(hg.E);
+    for (int i = 0; i < hg.E; ++i) cvar[i] = hg.evar[hg.cedge[i]];
+    return cvar;
 }
 
 // h_layer_of_check [C] may be null
@@ -78,11 +55,11 @@ inline int gnnd_graph_layers_host_checked(const int64_t* h_var, const int64_t* h
                                           int32_t* h_nlayers, int32_t* h_layer_of_check) {
     if (!h_var || !h_chk || !h_nlayers || num_edges <= 0 || V <= 0 || C <= 0)
         return GNND_ERR_INVALID_ARG;
-    GnndLayeredTables t;
-    const int rc = gnnd_layered_tables(h_var, h_chk, num_edges, V, C, t);
+    GnndHostGraph hg;                              // a check of degree 1 has its layer too
+    const int rc = gnnd_host_graph_build(h_var, h_chk, num_edges, V, C, hg);
     if (rc != GNND_OK) return rc;
     std::vector<int> layer_of;
-    *h_nlayers = gnnd_layers_build(V, C, t.cptr.data(), t.cvar.data(), layer_of);
+    *h_nlayers = gnnd_layers_build(V, C, hg.cptr.data(), gnnd_host_graph_cvar(hg).data(), layer_of);
     if (h_layer_of_check)
         for (int c = 0; c < C; ++c) h_layer_of_check[c] = layer_of[c];
     return GNND_OK;
@@ -95,13 +72,12 @@ int gnnd_minsum_layered_host_impl(const int64_t* h_var, const int64_t* h_chk, in
                                   int V, int C, const T* x, double alpha, double beta, int iters,
                                   int early_stop, T* out, T* llr, int32_t* iters_out,
                                   int32_t* status, int64_t batch, bool device_exp = false) {
-    GnndLayeredTables t;
-    const int rc = gnnd_layered_tables(h_var, h_chk, num_edges, V, C, t);
+    GnndHostGraph hg;
+    const int rc = gnnd_host_bp_graph_build(h_var, h_chk, num_edges, V, C, hg);
     if (rc != GNND_OK) return rc;
-    const int E = t.E;
-    const std::vector<int>&cptr = t.cptr, &cedge = t.cedge, &cvar = t.cvar;
-    for (int c = 0; c < C; ++c)
-        if (cptr[c + 1] - cptr[c] < 2) return GNND_ERR_UNSUPPORTED;
+    const int E = hg.E;
+    const std::vector<int>&cptr = hg.cptr, &cedge = hg.cedge;
+    const std::vector<int> cvar = gnnd_host_graph_cvar(hg);
     std::vector<int> layer_of, layer_ptr, order;
     const int nl = gnnd_layers_build(V, C, cptr.data(), cvar.data(), layer_of);
     gnnd_layers_order(C, nl, layer_of, layer_ptr, order);
@@ -132,30 +108,18 @@ int gnnd_minsum_layered_host_impl(const int64_t* h_var, const int64_t* h_chk, in
                 for (int i = cptr[c]; i < cptr[c + 1]; ++i) {
                     const int e = cedge[i], v = cvar[i];
                     const T q = L[v] - r[e];
-                    const T m = e == arg ? min2 : min1;
-                    const T am = a * m;
-                    const T d = am - bt;
-                    const T mag = d > T(0) ? d : T(0);
-                    const T rn = (par ^ (int)(q < T(0))) ? -mag : mag;
+                    const T rn = gnnd_minsum_signed_mag(a, bt, e == arg ? min2 : min1,
+                                                        par ^ (int)(q < T(0)));
                     L[v] = q + rn;
                     r[e] = rn;
                 }
             }
-            ok = 1;
-            for (int c = 0; c < C; ++c) {
-                int par = xc[c] < T(0);
-                for (int i = cptr[c]; i < cptr[c + 1]; ++i) par ^= (int)(L[cvar[i]] < T(0));
-                if (par) { ok = 0; break; }
-            }
+            ok = gnnd_syndrome_ok(hg, xc, L.data());
             if (early_stop && ok) break;
         }
         for (int v = 0; v < V; ++v) {
             if (llr) llr[b * V + v] = L[v];
-            if (!out) continue;
-            if (device_exp && sizeof(T) == sizeof(double))
-                out[b * V + v] = T(1) / (T(1) + (T)gnnd_exp_f64_device((double)L[v]));
-            else
-                out[b * V + v] = T(1) / (T(1) + (T)exp((double)L[v]));
+            if (out) out[b * V + v] = gnnd_soft_output(L[v], device_exp);
         }
         if (iters_out) iters_out[b] = it;
         if (status) status[b] = ok ? 0 : 1;
@@ -169,22 +133,19 @@ inline int gnnd_minsum_layered_host_checked(const int64_t* h_var, const int64_t*
                                             int32_t iters, int32_t early_stop, void* h_out,
                                             void* h_llr, int32_t* h_iters, int32_t* h_status,
                                             int64_t batch, bool device_exp = false) {
-    if (!h_var || !h_chk || num_edges <= 0 || num_var <= 0 || num_chk <= 0 || batch < 0)
-        return GNND_ERR_INVALID_ARG;
-    if (!gnnd_minsum_params_ok(alpha, beta, iters, early_stop)) return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(gnnd_host_list_ok(h_var, h_chk, num_edges, num_var, num_chk, batch) &&
+                                    gnnd_minsum_params_ok(alpha, beta, iters, early_stop),
+                                dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!h_x || !h_out) return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_F32)
-        return gnnd_minsum_layered_host_impl<float>(h_var, h_chk, num_edges, num_var, num_chk,
-                                                    (const float*)h_x, alpha, beta, iters,
-                                                    early_stop, (float*)h_out, (float*)h_llr,
-                                                    h_iters, h_status, batch, device_exp);
-    return gnnd_minsum_layered_host_impl<double>(h_var, h_chk, num_edges, num_var, num_chk,
-                                                 (const double*)h_x, alpha, beta, iters, early_stop,
-                                                 (double*)h_out, (double*)h_llr, h_iters, h_status,
-                                                 batch, device_exp);
+    return gnnd_by_dtype(dtype, [&](auto z) {
+        using T = decltype(z);
+        return gnnd_minsum_layered_host_impl<T>(h_var, h_chk, num_edges, num_var, num_chk,
+                                                (const T*)h_x, alpha, beta, iters, early_stop,
+                                                (T*)h_out, (T*)h_llr, h_iters, h_status, batch,
+                                                device_exp);
+    });
 }
 
 // gnnd_bposd_host_checked with the layered loop as its first stage
@@ -195,12 +156,11 @@ inline int gnnd_bposd_layered_host_checked(const int64_t* h_var, const int64_t* 
                                            int32_t order, void* h_pred, void* h_llr,
                                            int32_t* h_iters, int32_t* h_bp_status, void* h_ehat,
                                            int32_t* h_status, int32_t* h_choice, int64_t batch) {
-    if (!h_var || !h_chk || num_edges <= 0 || num_var <= 0 || num_chk <= 0 || batch < 0)
-        return GNND_ERR_INVALID_ARG;
-    if (!gnnd_bposd_params_ok(alpha, beta, iters, early_stop, base, method, order))
-        return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(
+        gnnd_host_list_ok(h_var, h_chk, num_edges, num_var, num_chk, batch) &&
+            gnnd_bposd_params_ok(alpha, beta, iters, early_stop, base, method, order),
+        dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!h_x || !h_pred || !h_llr || !h_bp_status || !h_ehat || !h_status)
         return GNND_ERR_INVALID_ARG;

@@ -2,12 +2,13 @@
 // the decoders' soft outputs into an estimate that satisfies the measured syndrome whenever one exists (order
 // 0), and among the higher-order candidates (combination sweep, exhaustive) the lightest one.
 #include "gnnd_common.h"
+#include "gnnd_wave_tile.h"
 #include "gnnd_osd_host.h"
 
 GNND_DEBUG_TU(osd)
 
 // ---------------------------------------------------------------------------------------
-// One wave per codeword, wave-private LDS, no workgroup barrier.  Per codeword:
+// The wave-private-tile plan of gnnd_wave_tile.h.  Per codeword:
 //   1. keys into LDS; every lane ranks its variables by counting (rank(v) = #{u : key_u > key_v
 //      or (key_u == key_v and u < v)}: a permutation, O(V^2 / 64) compares per lane) and scatters
 //      v to order[rank];
@@ -35,7 +36,6 @@ GNND_DEBUG_TU(osd)
 //      its mask leaves set.
 // ---------------------------------------------------------------------------------------
 constexpr int kOsdMaxRowsPerLane = 32;      // `used` is one 32-bit mask per lane: C <= 2048
-constexpr size_t kOsdLdsLimit = 64 * 1024;  // dynamic LDS of one workgroup without an opt-in
 
 struct OsdPlan {
     int words;        // column words per row, ceil(V / 32)
@@ -46,31 +46,21 @@ struct OsdPlan {
     int waves;        // waves per workgroup (0: the matrix does not fit)
 };
 
-static inline int osd_align16(int n) { return (n + 15) & ~15; }
-
 static OsdPlan osd_plan(int V, int C, size_t elem) {
     OsdPlan p;
     p.words = (V + 31) / 32;
     p.stride = (p.words + 1) | 1;
     p.rpl = (C + 63) / 64;
     const size_t a = (size_t)C * p.stride * 4;
-    p.off_key = osd_align16((int)(a > kOsdLdsLimit ? kOsdLdsLimit : a));
-    p.off_order = p.off_key + osd_align16(V * (int)elem);
-    p.off_piv = p.off_order + osd_align16(V * 2);
-    p.off_e = p.off_piv + osd_align16(C * 2);
-    p.wave_bytes = p.off_e + osd_align16(V);
-    p.waves = 0;
-    if (a <= kOsdLdsLimit && (size_t)p.wave_bytes <= kOsdLdsLimit && p.rpl <= kOsdMaxRowsPerLane) {
-        const int fit = (int)(kOsdLdsLimit / (size_t)p.wave_bytes);
-        p.waves = fit < 4 ? fit : 4;
-    }
+    // V, C <= 65535 and a is clamped to the limit: every offset fits an int
+    p.off_key = (int)wave_tile_align16(a > kWaveTileLdsLimit ? kWaveTileLdsLimit : a);
+    p.off_order = p.off_key + (int)wave_tile_align16((size_t)V * elem);
+    p.off_piv = p.off_order + (int)wave_tile_align16((size_t)V * 2);
+    p.off_e = p.off_piv + (int)wave_tile_align16((size_t)C * 2);
+    p.wave_bytes = p.off_e + (int)wave_tile_align16((size_t)V);
+    p.waves = a <= kWaveTileLdsLimit && p.rpl <= kOsdMaxRowsPerLane
+                  ? wave_tile_waves((size_t)p.wave_bytes) : 0;
     return p;
-}
-
-__device__ __forceinline__ void osd_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // one wave's tile
@@ -98,7 +88,7 @@ __device__ __forceinline__ void osd_keys_and_order(const OsdTile<T>& t, int V, i
         t.key[v] = p != p ? -(T)INFINITY : k;
         t.e[v] = (uint8_t)(hard && p > T(0.5));
     }
-    osd_wave_sync();
+    wave_tile_sync();
     for (int v = lane; v < V; v += 64) {
         const T kv = t.key[v];
         int rank = 0;
@@ -130,7 +120,7 @@ __device__ __forceinline__ void osd_build_rows(const OsdTile<T>& t, const GraphV
         }
         row[syn] = (uint32_t)par;
     }
-    osd_wave_sync();
+    wave_tile_sync();
 }
 
 // ---- phase 3: Gauss-Jordan over the ordered columns; returns the lane's pivot-row mask
@@ -172,7 +162,7 @@ __device__ __forceinline__ uint32_t osd_eliminate(const OsdTile<T>& t, const Osd
             for (int k = 0; k < pl.rpl; ++k)
                 if ((hit >> k) & 1u) A[(size_t)(lane + 64 * k) * S + w] ^= pw;
         }
-        osd_wave_sync();
+        wave_tile_sync();
     }
     return used;
 }
@@ -209,11 +199,11 @@ osd0_kernel(GraphView g, OsdPlan pl, int hard, const T* __restrict__ x,
                 if (r < C && ((used >> k) & 1u) && (A[(size_t)r * S + syn] & 1u))
                     s_e[GNND_DIDX((int)s_piv[r], V, GNND_DBG_VAR)] ^= 1;    // one pivot per column
             }
-        osd_wave_sync();
+        wave_tile_sync();
         T* eb = ehat + b * V;
         for (int v = lane; v < V; v += 64) eb[v] = s_e[v] ? T(1) : T(0);
         if (lane == 0) status[b] = fail ? 1 : 0;
-        osd_wave_sync();                    // tile reads done before the next codeword's writes
+        wave_tile_sync();                    // tile reads done before the next codeword's writes
     }
 }
 
@@ -280,7 +270,7 @@ __device__ __forceinline__ void osd_codeword(const OsdTile<T>& t, const GraphVie
             for (int k = 0; k < rpl; ++k)
                 if ((used >> k) & 1u)
                     s_e[GNND_DIDX((int)t.piv[lane + 64 * k], V, GNND_DBG_VAR)] |= 2;
-            osd_wave_sync();
+            wave_tile_sync();
             int F = 0;
             for (int base = 0; base < V; base += 64) {
                 const int pos = base + lane;
@@ -291,13 +281,13 @@ __device__ __forceinline__ void osd_codeword(const OsdTile<T>& t, const GraphVie
                     fr = !(s_e[v] & 2);
                 }
                 const unsigned long long m = __ballot(fr);
-                osd_wave_sync();        // every slot of the chunk read before one is rewritten
+                wave_tile_sync();        // every slot of the chunk read before one is rewritten
                 if (fr)
                     s_order[GNND_DIDX(F + __popcll(m & ((1ull << lane) - 1)), pos + 1,
                                       GNND_DBG_LDS_POS)] = (uint16_t)v;
                 F += __popcll(m);
             }
-            osd_wave_sync();
+            wave_tile_sync();
             GNND_DCHECK(F <= V, GNND_DBG_LDS_POS);
             // ---- candidates ----
             int best = osd_weight(smask & used, one);
@@ -355,14 +345,14 @@ __device__ __forceinline__ void osd_codeword(const OsdTile<T>& t, const GraphVie
             if ((used >> k) & (fm >> k) & 1u)
                 s_e[GNND_DIDX((int)t.piv[lane + 64 * k], V, GNND_DBG_VAR)] ^= 1;
     }
-    osd_wave_sync();
+    wave_tile_sync();
     T* eb = ehat + b * V;
     for (int v = lane; v < V; v += 64) eb[v] = (s_e[v] & 1) ? T(1) : T(0);
     if (lane == 0) {
         status[b] = fail ? 1 : 0;
         if (choice) choice[b] = best_idx;
     }
-    osd_wave_sync();                    // tile reads done before the next codeword's writes
+    wave_tile_sync();                    // tile reads done before the next codeword's writes
 }
 
 template <typename T>
@@ -492,19 +482,13 @@ osd_gated_kernel(GraphView g, OsdPlan pl, int hard, int method, int order,
     }
 }
 
-static unsigned osd_blocks(const OsdPlan& pl, int64_t B) {
-    const int64_t want = (B + pl.waves - 1) / pl.waves;
-    const int64_t cap = 8192 / pl.waves;                  // 32 waves per CU, grid-stride
-    return (unsigned)(want < cap ? want : cap);
-}
-
 template <typename T>
 static int launch_osd0(const gnnd_graph* g, const void* x, const void* pred, int base, void* ehat,
                        int32_t* status, int64_t B, hipStream_t st) {
     const GraphView& v = g->view;
     const OsdPlan pl = osd_plan(v.V, v.C, sizeof(T));
     if (pl.waves == 0) return GNND_ERR_UNSUPPORTED;
-    osd0_kernel<T><<<osd_blocks(pl, B), 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
+    osd0_kernel<T><<<wave_tile_blocks(B, pl.waves, pl.waves), 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
         v, pl, base == GNND_OSD_BASE_HARD, (const T*)x, (const T*)pred, (T*)ehat, status, B);
     GNND_LAUNCH_CHECK();
     return GNND_OK;
@@ -517,7 +501,7 @@ static int launch_osd(const gnnd_graph* g, const void* x, const void* pred, int 
     const GraphView& v = g->view;
     const OsdPlan pl = osd_plan(v.V, v.C, sizeof(T));
     if (pl.waves == 0) return GNND_ERR_UNSUPPORTED;
-    osd_kernel<T><<<osd_blocks(pl, B), 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
+    osd_kernel<T><<<wave_tile_blocks(B, pl.waves, pl.waves), 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
         v, pl, base == GNND_OSD_BASE_HARD, method, order, (const T*)x, (const T*)pred, (T*)ehat,
         status, choice, B);
     GNND_LAUNCH_CHECK();
@@ -526,16 +510,14 @@ static int launch_osd(const gnnd_graph* g, const void* x, const void* pred, int 
 
 extern "C" int gnnd_osd0(const gnnd_graph* g, int dtype, const void* d_x, const void* d_pred,
                          int base, void* d_ehat, int32_t* d_status, int64_t batch, void* stream) {
-    if (!g || batch < 0) return GNND_ERR_INVALID_ARG;
-    if (base != GNND_OSD_BASE_ZERO && base != GNND_OSD_BASE_HARD) return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(g && batch >= 0 && gnnd_osd_base_ok(base), dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!d_x || !d_pred || !d_ehat || !d_status) return GNND_ERR_INVALID_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == GNND_F32)
-        return launch_osd0<float>(g, d_x, d_pred, base, d_ehat, d_status, batch, st);
-    return launch_osd0<double>(g, d_x, d_pred, base, d_ehat, d_status, batch, st);
+    return gnnd_by_dtype(dtype, [&](auto z) {
+        return launch_osd0<decltype(z)>(g, d_x, d_pred, base, d_ehat, d_status, batch,
+                                        (hipStream_t)stream);
+    });
 }
 
 extern "C" int gnnd_osd0_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
@@ -549,19 +531,15 @@ extern "C" int gnnd_osd0_host(const int64_t* h_var, const int64_t* h_chk, int64_
 extern "C" int gnnd_osd(const gnnd_graph* g, int dtype, const void* d_x, const void* d_pred,
                         int base, int method, int32_t order, void* d_ehat, int32_t* d_status,
                         int32_t* d_choice, int64_t batch, void* stream) {
-    if (!g || batch < 0) return GNND_ERR_INVALID_ARG;
-    if (base != GNND_OSD_BASE_ZERO && base != GNND_OSD_BASE_HARD) return GNND_ERR_INVALID_ARG;
-    if (!gnnd_osd_order_ok(method, order)) return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(
+        g && batch >= 0 && gnnd_osd_base_ok(base) && gnnd_osd_order_ok(method, order), dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!d_x || !d_pred || !d_ehat || !d_status) return GNND_ERR_INVALID_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == GNND_F32)
-        return launch_osd<float>(g, d_x, d_pred, base, method, order, d_ehat, d_status, d_choice,
-                                 batch, st);
-    return launch_osd<double>(g, d_x, d_pred, base, method, order, d_ehat, d_status, d_choice,
-                              batch, st);
+    return gnnd_by_dtype(dtype, [&](auto z) {
+        return launch_osd<decltype(z)>(g, d_x, d_pred, base, method, order, d_ehat, d_status,
+                                       d_choice, batch, (hipStream_t)stream);
+    });
 }
 
 extern "C" int gnnd_osd_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
@@ -592,7 +570,7 @@ static int launch_osd_gated(const gnnd_graph* g, const void* x, const void* pred
     osd_gate_kernel<T><<<blocks, kGateThreads, 0, st>>>(v.V, gate, (const T*)pred, (const T*)llr,
                                                         (T*)ehat, status, choice, work, B);
     GNND_LAUNCH_CHECK();
-    osd_gated_kernel<T><<<osd_blocks(pl, B), 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
+    osd_gated_kernel<T><<<wave_tile_blocks(B, pl.waves, pl.waves), 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
         v, pl, base == GNND_OSD_BASE_HARD, method, order, (const T*)x, (const T*)pred, (T*)ehat,
         status, choice, work, B);
     GNND_LAUNCH_CHECK();
@@ -610,21 +588,18 @@ extern "C" int gnnd_osd_gated(const gnnd_graph* g, int dtype, const void* d_x, c
                               const void* d_llr, const int32_t* d_gate, int base, int method,
                               int32_t order, void* d_ehat, int32_t* d_status, int32_t* d_choice,
                               void* d_work, int64_t work_bytes, int64_t batch, void* stream) {
-    if (!g || batch < 0) return GNND_ERR_INVALID_ARG;
-    if (base != GNND_OSD_BASE_ZERO && base != GNND_OSD_BASE_HARD) return GNND_ERR_INVALID_ARG;
-    if (!gnnd_osd_order_ok(method, order)) return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(
+        g && batch >= 0 && gnnd_osd_base_ok(base) && gnnd_osd_order_ok(method, order), dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!d_x || !d_pred || !d_gate || !d_ehat || !d_status || !d_work) return GNND_ERR_INVALID_ARG;
     if (batch > kOsdGatedMaxBatch) return GNND_ERR_UNSUPPORTED;
     if (work_bytes < gnnd_osd_gated_bytes(batch)) return GNND_ERR_INVALID_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == GNND_F32)
-        return launch_osd_gated<float>(g, d_x, d_pred, d_llr, d_gate, base, method, order, d_ehat,
-                                       d_status, d_choice, (int32_t*)d_work, batch, st);
-    return launch_osd_gated<double>(g, d_x, d_pred, d_llr, d_gate, base, method, order, d_ehat,
-                                    d_status, d_choice, (int32_t*)d_work, batch, st);
+    return gnnd_by_dtype(dtype, [&](auto z) {
+        return launch_osd_gated<decltype(z)>(g, d_x, d_pred, d_llr, d_gate, base, method, order,
+                                             d_ehat, d_status, d_choice, (int32_t*)d_work, batch,
+                                             (hipStream_t)stream);
+    });
 }
 
 extern "C" int gnnd_osd_gated_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,

@@ -12,7 +12,11 @@
 #include <algorithm>
 #include <limits>
 #include <vector>
-#include "../../include/gnnd.h"
+#include "gnnd_host_args.h"
+
+inline bool gnnd_osd_base_ok(int base) {
+    return base == GNND_OSD_BASE_ZERO || base == GNND_OSD_BASE_HARD;
+}
 
 // method and order of gnnd_osd within the contract's limits
 inline bool gnnd_osd_order_ok(int method, int32_t order) {
@@ -182,20 +186,18 @@ inline int gnnd_osd0_host_checked(const int64_t* h_var, const int64_t* h_chk, in
                                   int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
                                   const void* h_pred, int base, void* h_ehat, int32_t* h_status,
                                   int64_t batch) {
-    if (!h_var || !h_chk || num_edges <= 0 || num_var <= 0 || num_chk <= 0 || batch < 0)
-        return GNND_ERR_INVALID_ARG;
-    if (base != GNND_OSD_BASE_ZERO && base != GNND_OSD_BASE_HARD) return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(
+        gnnd_host_list_ok(h_var, h_chk, num_edges, num_var, num_chk, batch) &&
+            gnnd_osd_base_ok(base),
+        dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!h_x || !h_pred || !h_ehat || !h_status) return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_F32)
-        return gnnd_osd0_host_impl<float>(h_var, h_chk, num_edges, num_var, num_chk,
-                                          (const float*)h_x, (const float*)h_pred, base,
-                                          (float*)h_ehat, h_status, batch);
-    return gnnd_osd0_host_impl<double>(h_var, h_chk, num_edges, num_var, num_chk,
-                                       (const double*)h_x, (const double*)h_pred, base,
-                                       (double*)h_ehat, h_status, batch);
+    return gnnd_by_dtype(dtype, [&](auto z) {
+        using T = decltype(z);
+        return gnnd_osd0_host_impl<T>(h_var, h_chk, num_edges, num_var, num_chk, (const T*)h_x,
+                                      (const T*)h_pred, base, (T*)h_ehat, h_status, batch);
+    });
 }
 
 inline int gnnd_osd_host_checked(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
@@ -203,21 +205,19 @@ inline int gnnd_osd_host_checked(const int64_t* h_var, const int64_t* h_chk, int
                                  const void* h_pred, int base, int method, int32_t order,
                                  void* h_ehat, int32_t* h_status, int32_t* h_choice,
                                  int64_t batch) {
-    if (!h_var || !h_chk || num_edges <= 0 || num_var <= 0 || num_chk <= 0 || batch < 0)
-        return GNND_ERR_INVALID_ARG;
-    if (base != GNND_OSD_BASE_ZERO && base != GNND_OSD_BASE_HARD) return GNND_ERR_INVALID_ARG;
-    if (!gnnd_osd_order_ok(method, order)) return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(
+        gnnd_host_list_ok(h_var, h_chk, num_edges, num_var, num_chk, batch) &&
+            gnnd_osd_base_ok(base) && gnnd_osd_order_ok(method, order),
+        dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!h_x || !h_pred || !h_ehat || !h_status) return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_F32)
-        return gnnd_osd_host_impl<float>(h_var, h_chk, num_edges, num_var, num_chk,
-                                         (const float*)h_x, (const float*)h_pred, base, method,
-                                         order, (float*)h_ehat, h_status, h_choice, batch);
-    return gnnd_osd_host_impl<double>(h_var, h_chk, num_edges, num_var, num_chk,
-                                      (const double*)h_x, (const double*)h_pred, base, method,
-                                      order, (double*)h_ehat, h_status, h_choice, batch);
+    return gnnd_by_dtype(dtype, [&](auto z) {
+        using T = decltype(z);
+        return gnnd_osd_host_impl<T>(h_var, h_chk, num_edges, num_var, num_chk, (const T*)h_x,
+                                     (const T*)h_pred, base, method, order, (T*)h_ehat, h_status,
+                                     h_choice, batch);
+    });
 }
 
 // ---- gated OSD (gnnd_osd_gated): scratch size and host mirror ----
@@ -271,21 +271,18 @@ inline int gnnd_osd_gated_host_checked(const int64_t* h_var, const int64_t* h_ch
                                        const void* h_llr, const int32_t* h_gate, int base,
                                        int method, int32_t order, void* h_ehat, int32_t* h_status,
                                        int32_t* h_choice, int64_t batch) {
-    if (!h_var || !h_chk || num_edges <= 0 || num_var <= 0 || num_chk <= 0 || batch < 0)
-        return GNND_ERR_INVALID_ARG;
-    if (base != GNND_OSD_BASE_ZERO && base != GNND_OSD_BASE_HARD) return GNND_ERR_INVALID_ARG;
-    if (!gnnd_osd_order_ok(method, order)) return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(
+        gnnd_host_list_ok(h_var, h_chk, num_edges, num_var, num_chk, batch) &&
+            gnnd_osd_base_ok(base) && gnnd_osd_order_ok(method, order),
+        dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!h_x || !h_pred || !h_gate || !h_ehat || !h_status) return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_F32)
-        return gnnd_osd_gated_host_impl<float>(h_var, h_chk, num_edges, num_var, num_chk,
-                                               (const float*)h_x, (const float*)h_pred,
-                                               (const float*)h_llr, h_gate, base, method, order,
-                                               (float*)h_ehat, h_status, h_choice, batch);
-    return gnnd_osd_gated_host_impl<double>(h_var, h_chk, num_edges, num_var, num_chk,
-                                            (const double*)h_x, (const double*)h_pred,
-                                            (const double*)h_llr, h_gate, base, method, order,
-                                            (double*)h_ehat, h_status, h_choice, batch);
+    return gnnd_by_dtype(dtype, [&](auto z) {
+        using T = decltype(z);
+        return gnnd_osd_gated_host_impl<T>(h_var, h_chk, num_edges, num_var, num_chk,
+                                           (const T*)h_x, (const T*)h_pred, (const T*)h_llr, h_gate,
+                                           base, method, order, (T*)h_ehat, h_status, h_choice,
+                                           batch);
+    });
 }

@@ -7,6 +7,7 @@
 // Built with -ffp-contract=off (Makefile XFLAGS_gnnd_relay): a * m - b is two roundings and
 // c * l + g * M three, on the device and in the host mirror alike.
 #include "gnnd_common.h"
+#include "gnnd_wave_tile.h"
 #include "gnnd_relay_host.h"
 
 // this translation unit's debug word: gnnd_debug_take_relay() (tests/relay_debug_worker.py reads it
@@ -14,8 +15,7 @@
 GNND_DEBUG_TU(relay)
 
 // ---------------------------------------------------------------------------------------
-// The plan of gnnd_minsum.hip: one wave per codeword, a wave-private LDS tile, wave fences only, a
-// grid-stride loop over codewords.  A wave's tile, all T:
+// The wave-private-tile plan and the min-sum steps of gnnd_wave_tile.h.  A wave's tile, all T:
 //   msg[E]   q_e and r_e in place
 //   pri[V]   the leg's prior term A_v = round(c_v * l_v) (l_v itself where g_v == 0), written
 //            once per leg
@@ -33,8 +33,6 @@ GNND_DEBUG_TU(relay)
 // Leaving a leg, and stopping after S solutions, are wave-uniform branches.  No index depends on
 // the data, so a NaN or an infinity in x or gammas stays inside its codeword.
 // ---------------------------------------------------------------------------------------
-constexpr size_t kRelayLdsLimit = 64 * 1024;    // dynamic LDS of one workgroup without an opt-in
-
 // the kernel's compile-time soft mode: none (gnnd_relay), or gnnd_relay_soft_mode + 1
 enum { kRelaySoftNone = 0, kRelaySoftLast = 1, kRelaySoftMean = 2 };
 
@@ -45,11 +43,10 @@ struct RelayPlan {
     int waves;                                 // waves per workgroup (0: the tile does not fit)
 };
 
-static inline size_t relay_align16(size_t n) { return (n + 15) & ~(size_t)15; }
-
 static RelayPlan relay_plan(int V, int E, size_t elem, int soft = kRelaySoftNone) {
     RelayPlan p;
-    const size_t msg = relay_align16((size_t)E * elem), node = relay_align16((size_t)V * elem);
+    const size_t msg = wave_tile_align16((size_t)E * elem);
+    const size_t node = wave_tile_align16((size_t)V * elem);
     // E, V <= 65535: far below overflow
     const size_t bytes = msg + (soft == kRelaySoftMean ? 5 : 4) * node;
     p.off_pri = (int)msg;
@@ -58,18 +55,8 @@ static RelayPlan relay_plan(int V, int E, size_t elem, int soft = kRelaySoftNone
     p.off_best = (int)(msg + 3 * node);
     p.off_acc = (int)(msg + 4 * node);
     p.wave_bytes = (int)bytes;
-    p.waves = 0;
-    if (bytes <= kRelayLdsLimit) {
-        const int fit = (int)(kRelayLdsLimit / bytes);
-        p.waves = fit < 4 ? fit : 4;
-    }
+    p.waves = wave_tile_waves(bytes);
     return p;
-}
-
-__device__ __forceinline__ void relay_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 struct RelayArgs {
@@ -94,8 +81,7 @@ relay_kernel(GraphView g, RelayPlan pl, RelayArgs ra, T a, T bt, const T* __rest
              const T* __restrict__ gammas, T* __restrict__ ehat, T* __restrict__ llr,
              RelaySoftOut<T> so, int64_t B) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int V = g.V, C = g.C, E = g.E, N = g.N;
-    (void)E;                                // read by the debug build's index checks only
+    const int V = g.V, N = g.N;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     char* tile = smem + (size_t)wave * pl.wave_bytes;
     T* s_msg = (T*)tile;
@@ -129,69 +115,30 @@ relay_kernel(GraphView g, RelayPlan pl, RelayArgs ra, T a, T bt, const T* __rest
                 s_gam[v] = gm;
                 const T gM = gm * s_llr[v];
                 const T sum = A + gM;                       // -ffp-contract=off: no fma
-                const T lam = gm == T(0) ? A : sum;
-                for (int e = g.var_ptr[v]; e < g.var_ptr[v + 1]; ++e)
-                    s_msg[GNND_DIDX(e, E, GNND_DBG_SLOT)] = lam;
+                bp_msg_fill(g, s_msg, v, gm == T(0) ? A : sum);
             }
-            relay_wave_sync();
+            wave_tile_sync();
             const int Tk = k == 0 ? ra.iters0 : ra.iters_leg;
             for (int it = 0; it < Tk; ++it) {
                 ++total;
-                // ---- check step (gnnd_minsum's) ----
-                for (int c = lane; c < C; c += 64) {
-                    const int i0 = g.chk_ptr[c], i1 = g.chk_ptr[c + 1];
-                    T min1 = (T)INFINITY, min2 = (T)INFINITY;
-                    int arg = -1;
-                    int par = xc[c] < T(0);
-                    for (int i = i0; i < i1; ++i) {
-                        const int e = GNND_DIDX(g.chk_edge[GNND_DIDX(i, E, GNND_DBG_SLOT)], E, GNND_DBG_SLOT);
-                        const T q = s_msg[e];
-                        const T aq = g_abs(q);
-                        par ^= (int)(q < T(0));
-                        if (aq < min1) { min2 = min1; min1 = aq; arg = e; }
-                        else if (aq < min2) min2 = aq;
-                    }
-                    for (int i = i0; i < i1; ++i) {
-                        const int e = GNND_DIDX(g.chk_edge[GNND_DIDX(i, E, GNND_DBG_SLOT)], E, GNND_DBG_SLOT);
-                        const T q = s_msg[e];
-                        const T m = e == arg ? min2 : min1;
-                        const T am = a * m;
-                        const T d = am - bt;                    // two roundings
-                        const T mag = d > T(0) ? d : T(0);
-                        s_msg[e] = (par ^ (int)(q < T(0))) ? -mag : mag;
-                    }
-                }
-                relay_wave_sync();
+                bp_check_step(g, s_msg, xc, a, bt, lane);
+                wave_tile_sync();
                 // ---- variable step: L_v = Lam_v(M) + r_e1 + ..., q_e = L_v - r_e, M_v = L_v ----
                 for (int v = lane; v < V; v += 64) {
                     const int e0 = g.var_ptr[v], e1 = g.var_ptr[v + 1];
                     const T A = s_pri[v], gm = s_gam[v];
                     const T gM = gm * s_llr[v];
                     const T sum = A + gM;
-                    T s = gm == T(0) ? A : sum;
-                    for (int e = e0; e < e1; ++e) s = s + s_msg[GNND_DIDX(e, E, GNND_DBG_SLOT)];
+                    const T s = bp_var_sum(g, s_msg, e0, e1, gm == T(0) ? A : sum);
                     s_llr[v] = s;
                     if (SOFT == kRelaySoftMean) {
                         const int vi = GNND_DIDX(v, V, GNND_DBG_VAR);
                         s_acc[vi] = s_acc[vi] + s;
                     }
-                    for (int e = e0; e < e1; ++e) {
-                        const int ei = GNND_DIDX(e, E, GNND_DBG_SLOT);
-                        s_msg[ei] = s - s_msg[ei];
-                    }
+                    bp_var_extrinsic(g, s_msg, e0, e1, s);
                 }
-                relay_wave_sync();
-                // ---- H^T h == t ? ----
-                int bad = 0;
-                for (int c = lane; c < C; c += 64) {
-                    int par = xc[c] < T(0);
-                    for (int i = g.chk_ptr[c]; i < g.chk_ptr[c + 1]; ++i) {
-                        const int e = GNND_DIDX(g.chk_edge[GNND_DIDX(i, E, GNND_DBG_SLOT)], E, GNND_DBG_SLOT);
-                        const int v = GNND_DIDX((int)(g.edge_vc[e] & 0xffffu), V, GNND_DBG_VAR);
-                        par ^= (int)(s_llr[v] < T(0));
-                    }
-                    bad |= par;
-                }
+                wave_tile_sync();
+                const int bad = bp_syndrome_bad(g, s_llr, xc, lane, 64);
                 if (__ballot(bad) != 0) continue;
                 // ---- a solution: its weight through the contract's tree; keep it if lighter ----
                 T p = T(0);
@@ -231,14 +178,8 @@ relay_kernel(GraphView g, RelayPlan pl, RelayArgs ra, T a, T bt, const T* __rest
             if (ra.leg) ra.leg[b] = bestk;
             if (ra.nsol) ra.nsol[b] = nsol;
         }
-        relay_wave_sync();                  // tile reads done before the next codeword's writes
+        wave_tile_sync();                  // tile reads done before the next codeword's writes
     }
-}
-
-static unsigned relay_blocks(const RelayPlan& pl, int64_t B) {
-    const int64_t want = (B + pl.waves - 1) / pl.waves;
-    const int64_t cap = 8192 / pl.waves;                  // 32 waves per CU, grid-stride
-    return (unsigned)(want < cap ? want : cap);
 }
 
 template <typename T, int SOFT>
@@ -249,7 +190,7 @@ static int launch_relay(const gnnd_graph* g, const RelayPlan& pl, const RelayArg
     const double total = (double)ra.iters0 + (double)(ra.legs - 1) * (double)ra.iters_leg;
     const RelaySoftOut<T> so = {(T*)pred, (T*)soft, (T)(1.0 / total)};
     relay_kernel<T, SOFT>
-        <<<relay_blocks(pl, B), 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
+        <<<wave_tile_blocks(B, pl.waves, pl.waves), 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
             g->view, pl, ra, (T)alpha, (T)beta, (const T*)x, (const T*)gammas, (T*)ehat, (T*)llr, so,
             B);
     GNND_LAUNCH_CHECK();
@@ -262,11 +203,10 @@ static int relay_run(const gnnd_graph* g, int dtype, const void* d_x, const void
                      double alpha, double beta, int soft_mode, void* d_pred, void* d_soft,
                      void* d_ehat, void* d_llr, int32_t* d_iters, int32_t* d_status, int32_t* d_leg,
                      int32_t* d_nsol, int64_t batch, void* stream) {
-    if (!g || batch < 0) return GNND_ERR_INVALID_ARG;
-    if (!gnnd_relay_params_ok(alpha, beta, legs, iters0, iters_leg, stop_after))
-        return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(
+        g && batch >= 0 && gnnd_relay_params_ok(alpha, beta, legs, iters0, iters_leg, stop_after),
+        dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!d_x || !d_gammas || !d_ehat || (soft_mode != kRelaySoftNone && !d_pred))
         return GNND_ERR_INVALID_ARG;
@@ -275,19 +215,17 @@ static int relay_run(const gnnd_graph* g, int dtype, const void* d_x, const void
                                     dtype == GNND_F32 ? sizeof(float) : sizeof(double), soft_mode);
     if (pl.waves == 0) return GNND_ERR_UNSUPPORTED;
     const RelayArgs ra = {legs, iters0, iters_leg, stop_after, d_iters, d_status, d_leg, d_nsol};
-    hipStream_t st = (hipStream_t)stream;
-#define RELAY_LAUNCH(T, SOFT)                                                                     \
+    return gnnd_by_dtype(dtype, [&](auto z) {
+        using T = decltype(z);
+        hipStream_t st = (hipStream_t)stream;
+#define RELAY_LAUNCH(SOFT)                                                                        \
     launch_relay<T, SOFT>(g, pl, ra, d_x, d_gammas, alpha, beta, d_ehat, d_llr, d_pred, d_soft,   \
                           batch, st)
-    if (dtype == GNND_F32) {
-        if (soft_mode == kRelaySoftNone) return RELAY_LAUNCH(float, kRelaySoftNone);
-        if (soft_mode == kRelaySoftLast) return RELAY_LAUNCH(float, kRelaySoftLast);
-        return RELAY_LAUNCH(float, kRelaySoftMean);
-    }
-    if (soft_mode == kRelaySoftNone) return RELAY_LAUNCH(double, kRelaySoftNone);
-    if (soft_mode == kRelaySoftLast) return RELAY_LAUNCH(double, kRelaySoftLast);
-    return RELAY_LAUNCH(double, kRelaySoftMean);
+        if (soft_mode == kRelaySoftNone) return RELAY_LAUNCH(kRelaySoftNone);
+        if (soft_mode == kRelaySoftLast) return RELAY_LAUNCH(kRelaySoftLast);
+        return RELAY_LAUNCH(kRelaySoftMean);
 #undef RELAY_LAUNCH
+    });
 }
 
 extern "C" int gnnd_relay(const gnnd_graph* g, int dtype, const void* d_x, const void* d_gammas,
@@ -353,12 +291,12 @@ extern "C" int gnnd_relay_osd(const gnnd_graph* g, int dtype, const void* d_x, c
                               int32_t* d_relay_status, int32_t* d_leg, int32_t* d_nsol,
                               void* d_ehat, int32_t* d_status, int32_t* d_choice, void* d_work,
                               int64_t work_bytes, int64_t batch, void* stream) {
-    if (!g || batch < 0) return GNND_ERR_INVALID_ARG;
-    if (!gnnd_relay_osd_params_ok(alpha, beta, legs, iters0, iters_leg, stop_after, soft, base,
-                                  method, order))
-        return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(
+        g && batch >= 0 &&
+            gnnd_relay_osd_params_ok(alpha, beta, legs, iters0, iters_leg, stop_after, soft, base,
+                                     method, order),
+        dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!d_x || !d_gammas || !d_pred || !d_llr || !d_relay_status || !d_ehat || !d_status ||
         !d_work)

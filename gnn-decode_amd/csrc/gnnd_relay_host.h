@@ -33,8 +33,7 @@ inline bool gnnd_relay_osd_params_ok(double alpha, double beta, int32_t legs, in
                                      int method, int32_t order) {
     if (!gnnd_relay_params_ok(alpha, beta, legs, iters0, iters_leg, stop_after)) return false;
     if (!gnnd_relay_soft_ok(soft)) return false;
-    if (base != GNND_OSD_BASE_ZERO && base != GNND_OSD_BASE_HARD) return false;
-    return gnnd_osd_order_ok(method, order);
+    return gnnd_osd_base_ok(base) && gnnd_osd_order_ok(method, order);
 }
 
 // weight(h) of the contract: 64 partials over v = j (mod 64) in ascending v, then the six-step
@@ -66,13 +65,11 @@ int gnnd_relay_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num
                          int64_t batch, int soft_mode = -1, T* pred = nullptr,
                          T* soft_out = nullptr, bool device_exp = false) {
     GnndHostGraph hg;
-    const int rc = gnnd_host_graph_build(h_var, h_chk, num_edges, V, C, hg);
+    const int rc = gnnd_host_bp_graph_build(h_var, h_chk, num_edges, V, C, hg);
     if (rc != GNND_OK) return rc;
-    const int E = hg.E;
-    const std::vector<int>&vptr = hg.vptr, &cptr = hg.cptr, &cedge = hg.cedge, &evar = hg.evar;
     const T a = (T)alpha, bt = (T)beta;
     const int N = V + C;
-    std::vector<T> msg(E), L(V), A(V), best(V);
+    std::vector<T> msg(hg.E), L(V), A(V), best(V);
     const bool mean = soft_mode == GNND_RELAY_SOFT_MEAN;
     std::vector<T> acc(mean ? V : 0);
     const T inv = (T)(1.0 / ((double)iters0 + (double)(legs - 1) * (double)iters_leg));
@@ -91,8 +88,8 @@ int gnnd_relay_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num
                 const T cl = c * xv[v];
                 A[v] = g[v] == T(0) ? xv[v] : cl;
             }
-            for (int e = 0; e < E; ++e) {
-                const int v = evar[e];
+            for (int e = 0; e < hg.E; ++e) {
+                const int v = hg.evar[e];
                 const T gm = g[v] * L[v];
                 const T lam = A[v] + gm;
                 msg[e] = g[v] == T(0) ? A[v] : lam;
@@ -100,42 +97,14 @@ int gnnd_relay_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num
             const int Tk = k == 0 ? iters0 : iters_leg;
             for (int it = 0; it < Tk; ++it) {
                 ++total;
-                for (int c = 0; c < C; ++c) {
-                    T min1 = std::numeric_limits<T>::infinity(), min2 = min1;
-                    int arg = -1, par = xc[c] < T(0);
-                    for (int i = cptr[c]; i < cptr[c + 1]; ++i) {
-                        const T q = msg[cedge[i]];
-                        const T aq = std::fabs(q);
-                        par ^= (int)(q < T(0));
-                        if (aq < min1) { min2 = min1; min1 = aq; arg = cedge[i]; }
-                        else if (aq < min2) min2 = aq;
-                    }
-                    for (int i = cptr[c]; i < cptr[c + 1]; ++i) {
-                        const int e = cedge[i];
-                        const T q = msg[e];
-                        const T m = e == arg ? min2 : min1;
-                        const T am = a * m;
-                        const T d = am - bt;
-                        const T mag = d > T(0) ? d : T(0);
-                        msg[e] = (par ^ (int)(q < T(0))) ? -mag : mag;
-                    }
-                }
+                gnnd_minsum_check_step(hg, xc, a, bt, msg.data());
                 for (int v = 0; v < V; ++v) {
                     const T gm = g[v] * L[v];
                     const T lam = A[v] + gm;
-                    T s = g[v] == T(0) ? A[v] : lam;
-                    for (int e = vptr[v]; e < vptr[v + 1]; ++e) s = s + msg[e];
-                    L[v] = s;
-                    if (mean) acc[v] = acc[v] + s;
-                    for (int e = vptr[v]; e < vptr[v + 1]; ++e) msg[e] = s - msg[e];
+                    L[v] = gnnd_minsum_var_update(hg, v, g[v] == T(0) ? A[v] : lam, msg.data());
+                    if (mean) acc[v] = acc[v] + L[v];
                 }
-                int ok = 1;
-                for (int c = 0; c < C; ++c) {
-                    int par = xc[c] < T(0);
-                    for (int i = cptr[c]; i < cptr[c + 1]; ++i) par ^= (int)(L[evar[cedge[i]]] < T(0));
-                    if (par) { ok = 0; break; }
-                }
-                if (ok) {
+                if (gnnd_syndrome_ok(hg, xc, L.data())) {
                     const T w = gnnd_relay_weight(L.data(), xv, V);
                     if (nsol == 0 || w < bestw) {                    // strict: a tie keeps the earlier
                         bestw = w;
@@ -159,10 +128,7 @@ int gnnd_relay_host_impl(const int64_t* h_var, const int64_t* h_chk, int64_t num
                 Z = Av * inv;                                        // one multiply
             }
             if (soft_out) soft_out[b * V + v] = Z;
-            if (device_exp && sizeof(T) == sizeof(double))
-                pred[b * V + v] = T(1) / (T(1) + (T)gnnd_exp_f64_device((double)Z));
-            else
-                pred[b * V + v] = T(1) / (T(1) + (T)exp((double)Z));
+            pred[b * V + v] = gnnd_soft_output(Z, device_exp);
         }
         if (iters_out) iters_out[b] = total;
         if (status) status[b] = nsol ? 0 : 1;
@@ -178,23 +144,20 @@ inline int gnnd_relay_host_checked(const int64_t* h_var, const int64_t* h_chk, i
                                    int32_t iters_leg, int32_t stop_after, double alpha, double beta,
                                    void* h_ehat, void* h_llr, int32_t* h_iters, int32_t* h_status,
                                    int32_t* h_leg, int32_t* h_nsol, int64_t batch) {
-    if (!h_var || !h_chk || num_edges <= 0 || num_var <= 0 || num_chk <= 0 || batch < 0)
-        return GNND_ERR_INVALID_ARG;
-    if (!gnnd_relay_params_ok(alpha, beta, legs, iters0, iters_leg, stop_after))
-        return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(
+        gnnd_host_list_ok(h_var, h_chk, num_edges, num_var, num_chk, batch) &&
+            gnnd_relay_params_ok(alpha, beta, legs, iters0, iters_leg, stop_after),
+        dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!h_x || !h_gammas || !h_ehat) return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_F32)
-        return gnnd_relay_host_impl<float>(h_var, h_chk, num_edges, num_var, num_chk,
-                                           (const float*)h_x, (const float*)h_gammas, legs, iters0,
-                                           iters_leg, stop_after, alpha, beta, (float*)h_ehat,
-                                           (float*)h_llr, h_iters, h_status, h_leg, h_nsol, batch);
-    return gnnd_relay_host_impl<double>(h_var, h_chk, num_edges, num_var, num_chk,
-                                        (const double*)h_x, (const double*)h_gammas, legs, iters0,
-                                        iters_leg, stop_after, alpha, beta, (double*)h_ehat,
-                                        (double*)h_llr, h_iters, h_status, h_leg, h_nsol, batch);
+    return gnnd_by_dtype(dtype, [&](auto z) {
+        using T = decltype(z);
+        return gnnd_relay_host_impl<T>(h_var, h_chk, num_edges, num_var, num_chk, (const T*)h_x,
+                                       (const T*)h_gammas, legs, iters0, iters_leg, stop_after,
+                                       alpha, beta, (T*)h_ehat, (T*)h_llr, h_iters, h_status, h_leg,
+                                       h_nsol, batch);
+    });
 }
 
 // gnnd_relay_soft_host: gnnd_relay_host's checks, then soft and h_pred.  The fp64 exponential is
@@ -207,26 +170,21 @@ inline int gnnd_relay_soft_host_checked(const int64_t* h_var, const int64_t* h_c
                                         void* h_pred, void* h_soft, void* h_ehat, void* h_llr,
                                         int32_t* h_iters, int32_t* h_status, int32_t* h_leg,
                                         int32_t* h_nsol, int64_t batch) {
-    if (!h_var || !h_chk || num_edges <= 0 || num_var <= 0 || num_chk <= 0 || batch < 0)
-        return GNND_ERR_INVALID_ARG;
-    if (!gnnd_relay_params_ok(alpha, beta, legs, iters0, iters_leg, stop_after) ||
-        !gnnd_relay_soft_ok(soft))
-        return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(
+        gnnd_host_list_ok(h_var, h_chk, num_edges, num_var, num_chk, batch) &&
+            gnnd_relay_params_ok(alpha, beta, legs, iters0, iters_leg, stop_after) &&
+            gnnd_relay_soft_ok(soft),
+        dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!h_x || !h_gammas || !h_ehat || !h_pred) return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_F32)
-        return gnnd_relay_host_impl<float>(h_var, h_chk, num_edges, num_var, num_chk,
-                                           (const float*)h_x, (const float*)h_gammas, legs, iters0,
-                                           iters_leg, stop_after, alpha, beta, (float*)h_ehat,
-                                           (float*)h_llr, h_iters, h_status, h_leg, h_nsol, batch,
-                                           soft, (float*)h_pred, (float*)h_soft, true);
-    return gnnd_relay_host_impl<double>(h_var, h_chk, num_edges, num_var, num_chk,
-                                        (const double*)h_x, (const double*)h_gammas, legs, iters0,
-                                        iters_leg, stop_after, alpha, beta, (double*)h_ehat,
-                                        (double*)h_llr, h_iters, h_status, h_leg, h_nsol, batch,
-                                        soft, (double*)h_pred, (double*)h_soft, true);
+    return gnnd_by_dtype(dtype, [&](auto z) {
+        using T = decltype(z);
+        return gnnd_relay_host_impl<T>(h_var, h_chk, num_edges, num_var, num_chk, (const T*)h_x,
+                                       (const T*)h_gammas, legs, iters0, iters_leg, stop_after,
+                                       alpha, beta, (T*)h_ehat, (T*)h_llr, h_iters, h_status, h_leg,
+                                       h_nsol, batch, soft, (T*)h_pred, (T*)h_soft, true);
+    });
 }
 
 // gnnd_relay_osd_host: the soft mirror, then gnnd_osd_gated_host with the relay status as the gate
@@ -239,13 +197,12 @@ inline int gnnd_relay_osd_host_checked(const int64_t* h_var, const int64_t* h_ch
                                        void* h_llr, int32_t* h_iters, int32_t* h_relay_status,
                                        int32_t* h_leg, int32_t* h_nsol, void* h_ehat,
                                        int32_t* h_status, int32_t* h_choice, int64_t batch) {
-    if (!h_var || !h_chk || num_edges <= 0 || num_var <= 0 || num_chk <= 0 || batch < 0)
-        return GNND_ERR_INVALID_ARG;
-    if (!gnnd_relay_osd_params_ok(alpha, beta, legs, iters0, iters_leg, stop_after, soft, base,
-                                  method, order))
-        return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(
+        gnnd_host_list_ok(h_var, h_chk, num_edges, num_var, num_chk, batch) &&
+            gnnd_relay_osd_params_ok(alpha, beta, legs, iters0, iters_leg, stop_after, soft, base,
+                                     method, order),
+        dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!h_x || !h_gammas || !h_pred || !h_llr || !h_relay_status || !h_ehat || !h_status)
         return GNND_ERR_INVALID_ARG;

@@ -2,6 +2,7 @@
 // clusters around the defects by half-edges, merge them, peel a spanning forest.  Integers only;
 // every output is bit-reproducible and equal to the host mirror's (gnnd_uf_host.h).
 #include "gnnd_common.h"
+#include "gnnd_wave_tile.h"
 #include "gnnd_uf_host.h"
 
 // this translation unit's debug word: gnnd_debug_take_uf() (tests/uf_debug_worker.py reads it next
@@ -9,8 +10,7 @@
 GNND_DEBUG_TU(uf)
 
 // ---------------------------------------------------------------------------------------
-// The plan of gnnd_bpgd.hip: one wave per codeword, a wave-private LDS tile, wave fences only, a
-// grid-stride loop over codewords.  A wave's tile, all int32:
+// The wave-private-tile plan of gnnd_wave_tile.h.  A wave's tile, all int32:
 //   grow[V]     half-edges grown on edge v: 0, 1, 2 (full)
 //   label[N]    the cluster of vertex u = the highest vertex index in it
 //   par[N]      defect[u]; during the peel the XOR of the defects over u's subtree
@@ -29,38 +29,24 @@ GNND_DEBUG_TU(uf)
 // clamps nothing; the debug build checks every one of these).  The endpoint and virtual-vertex
 // tables come from the host builder, which the CPU tests check.
 // ---------------------------------------------------------------------------------------
-constexpr size_t kUfLdsLimit = 64 * 1024;       // dynamic LDS of one workgroup without an opt-in
-
 struct UfPlan {
     int off_label, off_par, off_aux, off_parent;    // byte offsets inside one wave's tile (grow at 0)
     int wave_bytes;                                 // one wave's tile (16-byte multiple)
     int waves;                                      // waves per workgroup (0: the tile does not fit)
 };
 
-static inline size_t uf_align16(size_t n) { return (n + 15) & ~(size_t)15; }
-
 static UfPlan uf_plan(int V, int N) {
     UfPlan p;
-    const size_t edge = uf_align16((size_t)V * sizeof(int32_t));
-    const size_t node = uf_align16((size_t)N * sizeof(int32_t));
+    const size_t edge = wave_tile_align16((size_t)V * sizeof(int32_t));
+    const size_t node = wave_tile_align16((size_t)N * sizeof(int32_t));
     const size_t bytes = edge + 4 * node;           // V <= 65535, N <= 131070: far below overflow
     p.off_label = (int)edge;
     p.off_par = (int)(edge + node);
     p.off_aux = (int)(edge + 2 * node);
     p.off_parent = (int)(edge + 3 * node);
     p.wave_bytes = (int)bytes;
-    p.waves = 0;
-    if (bytes <= kUfLdsLimit) {
-        const int fit = (int)(kUfLdsLimit / bytes);
-        p.waves = fit < 4 ? fit : 4;
-    }
+    p.waves = wave_tile_waves(bytes);
     return p;
-}
-
-__device__ __forceinline__ void uf_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 struct UfArgs {
@@ -97,21 +83,21 @@ uf_kernel(UfPlan pl, UfArgs ua, const T* __restrict__ x, T* __restrict__ ehat, i
             s_par[u] = u < C ? (int)(xc[u] < T(0)) : 0;
         }
         for (int v = lane; v < V; v += 64) s_grow[v] = 0;
-        uf_wave_sync();
+        wave_tile_sync();
         // ---- a virtual vertex's defect: the XOR of t over its component's checks ----
         for (int c = lane; c < C; c += 64) {
             const int vv = ua.cvirt[c];
             if (vv >= 0 && s_par[c]) atomicXor(&s_par[GNND_DIDX(vv, N, GNND_DBG_NODE)], 1);
         }
-        uf_wave_sync();
+        wave_tile_sync();
         int rounds = 0, status = 0;
         for (;;) {
             // ---- odd[l] = XOR of defect[u] over label[u] == l ----
             for (int u = lane; u < N; u += 64) s_aux[u] = 0;
-            uf_wave_sync();
+            wave_tile_sync();
             for (int u = lane; u < N; u += 64)
                 if (s_par[u]) atomicXor(&s_aux[GNND_DIDX(s_label[u], N, GNND_DBG_NODE)], 1);
-            uf_wave_sync();
+            wave_tile_sync();
             int any = 0;
             for (int u = lane; u < N; u += 64) any |= s_aux[u];
             if (__ballot(any) == 0) break;
@@ -130,7 +116,7 @@ uf_kernel(UfPlan pl, UfArgs ua, const T* __restrict__ x, T* __restrict__ ehat, i
             // an odd cluster with no edge left to grow is a whole component: no e satisfies t
             if (__ballot(grew) == 0) { status = 1; break; }
             ++rounds;
-            uf_wave_sync();
+            wave_tile_sync();
             // ---- labels: the fixed point of label <- max over the full edges ----
             for (;;) {
                 int changed = 0;
@@ -143,17 +129,17 @@ uf_kernel(UfPlan pl, UfArgs ua, const T* __restrict__ x, T* __restrict__ ehat, i
                     atomicMax(la < lb ? &s_label[a] : &s_label[bb], la < lb ? lb : la);
                     changed = 1;
                 }
-                uf_wave_sync();
+                wave_tile_sync();
                 if (__ballot(changed) == 0) break;
             }
         }
         // ---- forest: depth[u] = BFS distance from the label vertex over the full edges ----
-        uf_wave_sync();                                     // the odd[] reads are done
+        wave_tile_sync();                                     // the odd[] reads are done
         for (int u = lane; u < N; u += 64) {
             s_aux[u] = s_label[u] == u ? 0 : kGnndUfInf;
             s_parent[u] = V;
         }
-        uf_wave_sync();
+        wave_tile_sync();
         for (;;) {
             int changed = 0;
             for (int v = lane; v < V; v += 64) {
@@ -164,7 +150,7 @@ uf_kernel(UfPlan pl, UfArgs ua, const T* __restrict__ x, T* __restrict__ ehat, i
                 if (da + 1 < db) { atomicMin(&s_aux[bb], da + 1); changed = 1; }
                 if (db + 1 < da) { atomicMin(&s_aux[a], db + 1); changed = 1; }
             }
-            uf_wave_sync();
+            wave_tile_sync();
             if (__ballot(changed) == 0) break;
         }
         // ---- parent edge: the lowest full edge to a vertex one level up; nfull; the deepest level ----
@@ -189,7 +175,7 @@ uf_kernel(UfPlan pl, UfArgs ua, const T* __restrict__ x, T* __restrict__ ehat, i
             maxd = o > maxd ? o : maxd;
         }
         maxd = maxd < N ? maxd : N - 1;                     // a depth is below N: bounds the loop
-        uf_wave_sync();
+        wave_tile_sync();
         // ---- peel: subtree parities, the deepest level first ----
         for (int d = maxd; d >= 1; --d) {
             for (int u = lane; u < N; u += 64) {
@@ -198,7 +184,7 @@ uf_kernel(UfPlan pl, UfArgs ua, const T* __restrict__ x, T* __restrict__ ehat, i
                 const int a = ends[2 * e], bb = ends[2 * e + 1];
                 atomicXor(&s_par[GNND_DIDX(a == u ? bb : a, N, GNND_DBG_NODE)], 1);
             }
-            uf_wave_sync();
+            wave_tile_sync();
         }
         // ---- outputs: edge v is set where it is the parent edge of an end with an odd subtree ----
         for (int v = lane; v < V; v += 64) {
@@ -215,20 +201,14 @@ uf_kernel(UfPlan pl, UfArgs ua, const T* __restrict__ x, T* __restrict__ ehat, i
             if (ua.status) ua.status[b] = status;
             if (ua.nfull) ua.nfull[b] = nfull;
         }
-        uf_wave_sync();                     // tile reads done before the next codeword's writes
+        wave_tile_sync();                     // tile reads done before the next codeword's writes
     }
-}
-
-static unsigned uf_blocks(const UfPlan& pl, int64_t B) {
-    const int64_t want = (B + pl.waves - 1) / pl.waves;
-    const int64_t cap = 8192 / pl.waves;                  // 32 waves per CU, grid-stride
-    return (unsigned)(want < cap ? want : cap);
 }
 
 template <typename T>
 static int launch_uf(const UfPlan& pl, const UfArgs& ua, const void* x, void* ehat, int64_t B,
                      hipStream_t st) {
-    uf_kernel<T><<<uf_blocks(pl, B), 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
+    uf_kernel<T><<<wave_tile_blocks(B, pl.waves, pl.waves), 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
         pl, ua, (const T*)x, (T*)ehat, B);
     GNND_LAUNCH_CHECK();
     return GNND_OK;
@@ -237,9 +217,8 @@ static int launch_uf(const UfPlan& pl, const UfArgs& ua, const void* x, void* eh
 extern "C" int gnnd_uf(const gnnd_graph* g, int dtype, const void* d_x, const int32_t* d_gate,
                        void* d_ehat, int32_t* d_rounds, int32_t* d_status, int32_t* d_nfull,
                        int64_t batch, void* stream) {
-    if (!g || batch < 0) return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int rc = gnnd_args_rc(g && batch >= 0, dtype);
+    if (rc != GNND_OK) return rc;
     if (batch == 0) return GNND_OK;
     if (!d_x || !d_ehat) return GNND_ERR_INVALID_ARG;
     if (g->uf_nvert == 0) return GNND_ERR_UNSUPPORTED;      // not matchable
@@ -248,9 +227,9 @@ extern "C" int gnnd_uf(const gnnd_graph* g, int dtype, const void* d_x, const in
     if (pl.waves == 0) return GNND_ERR_UNSUPPORTED;
     const UfArgs ua = {V, C, g->uf_nvert, g->uf_dev, g->uf_dev + 2 * V, d_gate,
                        d_rounds, d_status, d_nfull};
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == GNND_F32) return launch_uf<float>(pl, ua, d_x, d_ehat, batch, st);
-    return launch_uf<double>(pl, ua, d_x, d_ehat, batch, st);
+    return gnnd_by_dtype(dtype, [&](auto z) {
+        return launch_uf<decltype(z)>(pl, ua, d_x, d_ehat, batch, (hipStream_t)stream);
+    });
 }
 
 extern "C" int gnnd_uf_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,

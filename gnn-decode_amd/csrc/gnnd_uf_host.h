@@ -8,7 +8,7 @@
 #pragma once
 #include <stdint.h>
 #include <vector>
-#include "../../include/gnnd.h"
+#include "gnnd_host_args.h"
 
 constexpr int kGnndUfInf = 0x3fffffff;      // depth of a vertex no sweep has reached yet
 
@@ -199,18 +199,17 @@ inline int gnnd_uf_host_checked(const int64_t* h_var, const int64_t* h_chk, int6
                                 int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
                                 const int32_t* h_gate, void* h_ehat, int32_t* h_rounds,
                                 int32_t* h_status, int32_t* h_nfull, int64_t batch) {
-    if (!h_var || !h_chk || num_edges <= 0 || num_var <= 0 || num_chk <= 0 || batch < 0)
-        return GNND_ERR_INVALID_ARG;
-    if (dtype == GNND_BF16) return GNND_ERR_UNSUPPORTED;
-    if (dtype != GNND_F32 && dtype != GNND_F64) return GNND_ERR_INVALID_ARG;
+    const int arc = gnnd_args_rc(
+        gnnd_host_list_ok(h_var, h_chk, num_edges, num_var, num_chk, batch), dtype);
+    if (arc != GNND_OK) return arc;
     if (batch == 0) return GNND_OK;
     if (!h_x || !h_ehat) return GNND_ERR_INVALID_ARG;
     GnndUfGraph ug;
     const int rc = gnnd_uf_graph_build(h_var, h_chk, num_edges, num_var, num_chk, ug);
     if (rc != GNND_OK) return rc;
-    if (dtype == GNND_F32)
-        return gnnd_uf_host_impl<float>(ug, (const float*)h_x, h_gate, (float*)h_ehat, h_rounds,
-                                        h_status, h_nfull, batch);
-    return gnnd_uf_host_impl<double>(ug, (const double*)h_x, h_gate, (double*)h_ehat, h_rounds,
-                                     h_status, h_nfull, batch);
+    return gnnd_by_dtype(dtype, [&](auto z) {
+        using T = decltype(z);
+        return gnnd_uf_host_impl<T>(ug, (const T*)h_x, h_gate, (T*)h_ehat, h_rounds, h_status,
+                                    h_nfull, batch);
+    });
 }
