@@ -7,6 +7,7 @@
 #include "gnnd_wave_tile.h"
 #include "gnnd_minsum_host.h"
 #include "gnnd_bposd_host.h"
+#include "gnnd_ufw_host.h"
 
 // this translation unit's debug word: gnnd_debug_take_minsum() (the collector list of
 // gnnd_debug_flags lives in the decoder's translation unit, which this feature leaves alone;
@@ -181,4 +182,47 @@ extern "C" int gnnd_bposd_host(const int64_t* h_var, const int64_t* h_chk, int64
     return gnnd_bposd_host_checked(h_var, h_chk, num_edges, num_var, num_chk, dtype, h_x, alpha,
                                    beta, iters, early_stop, base, method, order, h_pred, h_llr,
                                    h_iters, h_bp_status, h_ehat, h_status, h_choice, batch);
+}
+
+// ---------------------------------------------------------------------------------------
+// gnnd_belief_find: gnnd_minsum, then gnnd_ufw on the min-sum posteriors with the min-sum status as
+// the gate, passing the converged codewords through.  Every refusal of either stage is decided
+// here, before the first launch.
+// ---------------------------------------------------------------------------------------
+bool gnnd_uf_fits(const gnnd_graph* g);     // gnnd_ufw.hip: matchable, and the tile of gnnd_uf fits
+
+extern "C" int gnnd_belief_find(const gnnd_graph* g, int dtype, const void* d_x, double alpha,
+                                double beta, int32_t iters, int32_t early_stop, double scale,
+                                int32_t wmax, void* d_pred, void* d_llr, int32_t* d_iters,
+                                int32_t* d_bp_status, void* d_ehat, int32_t* d_status,
+                                int32_t* d_rounds, int32_t* d_nfull, int32_t* d_events,
+                                int64_t batch, void* stream) {
+    const int rc = gnnd_args_rc(g && batch >= 0 &&
+                                    gnnd_minsum_params_ok(alpha, beta, iters, early_stop) &&
+                                    gnnd_ufw_params_ok(scale, wmax, 1),
+                                dtype);
+    if (rc != GNND_OK) return rc;
+    if (batch == 0) return GNND_OK;
+    if (!d_x || !d_pred || !d_llr || !d_bp_status || !d_ehat) return GNND_ERR_INVALID_ARG;
+    const size_t elem = dtype == GNND_F32 ? sizeof(float) : sizeof(double);
+    if (g->min_dc < 2 || minsum_plan(g->view.V, g->view.E, elem).waves == 0 || !gnnd_uf_fits(g))
+        return GNND_ERR_UNSUPPORTED;
+    const int st = gnnd_minsum(g, dtype, d_x, alpha, beta, iters, early_stop, d_pred, d_llr,
+                               d_iters, d_bp_status, batch, stream);
+    if (st != GNND_OK) return st;
+    return gnnd_ufw(g, dtype, d_x, d_llr, scale, wmax, d_bp_status, 1, d_ehat, d_rounds, d_status,
+                    d_nfull, d_events, batch, stream);
+}
+
+extern "C" int gnnd_belief_find_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                                     int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                                     double alpha, double beta, int32_t iters, int32_t early_stop,
+                                     double scale, int32_t wmax, void* h_pred, void* h_llr,
+                                     int32_t* h_iters, int32_t* h_bp_status, void* h_ehat,
+                                     int32_t* h_status, int32_t* h_rounds, int32_t* h_nfull,
+                                     int32_t* h_events, int64_t batch) {
+    return gnnd_belief_find_host_checked(h_var, h_chk, num_edges, num_var, num_chk, dtype, h_x,
+                                         alpha, beta, iters, early_stop, scale, wmax, h_pred, h_llr,
+                                         h_iters, h_bp_status, h_ehat, h_status, h_rounds, h_nfull,
+                                         h_events, batch);
 }

@@ -82,57 +82,62 @@ inline int gnnd_graph_matching_host_checked(const int64_t* h_var, const int64_t*
     return GNND_OK;
 }
 
+// grow [V] is the decoder's own growth state of an edge (gnnd_uf: the half-edges grown, full is 2;
+// gnnd_ufw: the length that remains, full is 0): the shared steps read it through a predicate
 struct GnndUfState {
     std::vector<int> grow, label, par, odd, depth, parent;
 };
 
-// One codeword: t [C] the syndrome bits -> ehat01 [V], and rounds / status / nfull.
-inline void gnnd_uf_decode_one(const GnndUfGraph& ug, const unsigned char* t, GnndUfState& s,
-                               unsigned char* ehat01, int32_t* rounds_out, int32_t* status_out,
-                               int32_t* nfull_out) {
-    const int V = ug.V, C = ug.C, N = ug.N;
-    const int* ends = ug.ends.data();
-    s.grow.assign(V, 0);
+// label[u] = u, defect[u] = t_u, a virtual vertex's defect the XOR of t over its component's
+// checks; sizes the state.  The caller fills s.grow.
+inline void gnnd_uf_setup(const GnndUfGraph& ug, const unsigned char* t, GnndUfState& s) {
+    const int C = ug.C, N = ug.N;
     s.label.resize(N);
     s.par.assign(N, 0);
     s.odd.resize(N);
     s.depth.resize(N);
     s.parent.resize(N);
-    std::vector<int>&grow = s.grow, &label = s.label, &par = s.par, &odd = s.odd;
-    std::vector<int>&depth = s.depth, &parent = s.parent;
-    for (int u = 0; u < N; ++u) label[u] = u;
+    for (int u = 0; u < N; ++u) s.label[u] = u;
     for (int c = 0; c < C; ++c) {
-        par[c] = t[c];
-        if (t[c] && ug.cvirt[c] >= 0) par[ug.cvirt[c]] ^= 1;
+        s.par[c] = t[c];
+        if (t[c] && ug.cvirt[c] >= 0) s.par[ug.cvirt[c]] ^= 1;
     }
-    int rounds = 0, status = 0;
-    for (;;) {
-        for (int u = 0; u < N; ++u) odd[u] = 0;
-        for (int u = 0; u < N; ++u) odd[label[u]] ^= par[u];
-        bool any = false;
-        for (int u = 0; u < N; ++u) any = any || odd[u];
-        if (!any) break;
-        bool grew = false;
-        for (int v = 0; v < V; ++v) {
-            const int g = grow[v] + odd[label[ends[2 * v]]] + odd[label[ends[2 * v + 1]]];
-            const int ng = g < 2 ? g : 2;
-            grew = grew || ng != grow[v];
-            grow[v] = ng;
-        }
-        if (!grew) { status = 1; break; }        // an odd cluster that is a whole component
-        ++rounds;
-        for (bool changed = true; changed;) {
-            changed = false;
-            for (int v = 0; v < V; ++v) {
-                if (grow[v] != 2) continue;
-                const int a = ends[2 * v], b = ends[2 * v + 1];
-                if (label[a] == label[b]) continue;
-                label[a] = label[b] = label[a] > label[b] ? label[a] : label[b];
-                changed = true;
-            }
+}
+
+// odd[l] = XOR of defect[u] over label[u] == l; is any cluster odd
+inline bool gnnd_uf_cluster_parities(const GnndUfGraph& ug, GnndUfState& s) {
+    const int N = ug.N;
+    for (int u = 0; u < N; ++u) s.odd[u] = 0;
+    for (int u = 0; u < N; ++u) s.odd[s.label[u]] ^= s.par[u];
+    bool any = false;
+    for (int u = 0; u < N; ++u) any = any || s.odd[u];
+    return any;
+}
+
+// labels: the fixed point of label <- max over the full edges; full(s.grow[v]) says which they are
+template <typename Full>
+void gnnd_uf_merge_labels(const GnndUfGraph& ug, GnndUfState& s, Full full) {
+    const int* ends = ug.ends.data();
+    for (bool changed = true; changed;) {
+        changed = false;
+        for (int v = 0; v < ug.V; ++v) {
+            if (!full(s.grow[v])) continue;
+            const int a = ends[2 * v], b = ends[2 * v + 1];
+            if (s.label[a] == s.label[b]) continue;
+            s.label[a] = s.label[b] = s.label[a] > s.label[b] ? s.label[a] : s.label[b];
+            changed = true;
         }
     }
-    // forest: BFS depth from the label vertex, the lowest full edge one level up as the parent
+}
+
+// Once growth has ended: the forest (BFS depth from the label vertex, the lowest full edge one
+// level up as the parent), the peel and ehat01 [V]; returns the number of full edges.
+template <typename Full>
+int gnnd_uf_forest_peel(const GnndUfGraph& ug, GnndUfState& s, Full full, unsigned char* ehat01) {
+    const int V = ug.V, N = ug.N;
+    const int* ends = ug.ends.data();
+    std::vector<int>&grow = s.grow, &label = s.label, &par = s.par;
+    std::vector<int>&depth = s.depth, &parent = s.parent;
     for (int u = 0; u < N; ++u) {
         depth[u] = label[u] == u ? 0 : kGnndUfInf;
         parent[u] = V;
@@ -140,7 +145,7 @@ inline void gnnd_uf_decode_one(const GnndUfGraph& ug, const unsigned char* t, Gn
     for (bool changed = true; changed;) {
         changed = false;
         for (int v = 0; v < V; ++v) {
-            if (grow[v] != 2) continue;
+            if (!full(grow[v])) continue;
             const int a = ends[2 * v], b = ends[2 * v + 1];
             if (depth[a] + 1 < depth[b]) { depth[b] = depth[a] + 1; changed = true; }
             if (depth[b] + 1 < depth[a]) { depth[a] = depth[b] + 1; changed = true; }
@@ -148,7 +153,7 @@ inline void gnnd_uf_decode_one(const GnndUfGraph& ug, const unsigned char* t, Gn
     }
     int nfull = 0, maxd = 0;
     for (int v = 0; v < V; ++v) {
-        if (grow[v] != 2) continue;
+        if (!full(grow[v])) continue;
         ++nfull;
         const int a = ends[2 * v], b = ends[2 * v + 1];
         if (depth[a] + 1 == depth[b] && v < parent[b]) parent[b] = v;
@@ -166,12 +171,38 @@ inline void gnnd_uf_decode_one(const GnndUfGraph& ug, const unsigned char* t, Gn
     for (int v = 0; v < V; ++v) {
         const int a = ends[2 * v], b = ends[2 * v + 1];
         int h = 0;
-        if (grow[v] == 2) h = parent[a] == v ? par[a] : parent[b] == v ? par[b] : 0;
+        if (full(grow[v])) h = parent[a] == v ? par[a] : parent[b] == v ? par[b] : 0;
         ehat01[v] = (unsigned char)h;
     }
+    return nfull;
+}
+
+// One codeword: t [C] the syndrome bits -> ehat01 [V], and rounds / status / nfull.
+inline void gnnd_uf_decode_one(const GnndUfGraph& ug, const unsigned char* t, GnndUfState& s,
+                               unsigned char* ehat01, int32_t* rounds_out, int32_t* status_out,
+                               int32_t* nfull_out) {
+    const int V = ug.V;
+    const int* ends = ug.ends.data();
+    const auto full = [](int g) { return g == 2; };
+    s.grow.assign(V, 0);
+    gnnd_uf_setup(ug, t, s);
+    std::vector<int>&grow = s.grow, &label = s.label, &odd = s.odd;
+    int rounds = 0, status = 0;
+    while (gnnd_uf_cluster_parities(ug, s)) {
+        bool grew = false;
+        for (int v = 0; v < V; ++v) {
+            const int g = grow[v] + odd[label[ends[2 * v]]] + odd[label[ends[2 * v + 1]]];
+            const int ng = g < 2 ? g : 2;
+            grew = grew || ng != grow[v];
+            grow[v] = ng;
+        }
+        if (!grew) { status = 1; break; }        // an odd cluster that is a whole component
+        ++rounds;
+        gnnd_uf_merge_labels(ug, s, full);
+    }
+    *nfull_out = gnnd_uf_forest_peel(ug, s, full, ehat01);
     *rounds_out = rounds;
     *status_out = status;
-    *nfull_out = nfull;
 }
 
 // every output but ehat may be null; gate may be null

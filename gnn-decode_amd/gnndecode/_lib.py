@@ -143,6 +143,17 @@ SIGNATURES = {
     'gnnd_uf': (_int, [_vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     'gnnd_uf_host': (_int, [_c_i64p, _c_i64p, _i64, _i32, _i32, _int, _vp, _c_i32p, _vp, _c_i32p,
                             _c_i32p, _c_i32p, _i64]),
+    'gnnd_ufw': (_int, [_vp, _int, _vp, _vp, ctypes.c_double, _i32, _vp, _i32, _vp, _vp, _vp, _vp,
+                        _vp, _i64, _vp]),
+    'gnnd_ufw_host': (_int, [_c_i64p, _c_i64p, _i64, _i32, _i32, _int, _vp, _vp, ctypes.c_double,
+                             _i32, _c_i32p, _i32, _vp, _c_i32p, _c_i32p, _c_i32p, _c_i32p, _i64]),
+    'gnnd_belief_find': (_int, [_vp, _int, _vp, ctypes.c_double, ctypes.c_double, _i32, _i32,
+                                ctypes.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _i64, _vp]),
+    'gnnd_belief_find_host': (_int, [_c_i64p, _c_i64p, _i64, _i32, _i32, _int, _vp,
+                                     ctypes.c_double, ctypes.c_double, _i32, _i32, ctypes.c_double,
+                                     _i32, _vp, _vp, _c_i32p, _c_i32p, _vp, _c_i32p, _c_i32p,
+                                     _c_i32p, _c_i32p, _i64]),
     'gnnd_v24_check_mlp_table':(_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     'gnnd_adam_step': (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double,
                               ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp]),

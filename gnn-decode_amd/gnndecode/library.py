@@ -49,6 +49,12 @@ a custom op costs more than the 0.47 ms headline kernel, measured r02n):
   gnnd::uf(graph_id, x, gate?) -> (ehat, rounds, status, nfull)   the union-find decoder of a
       matchable graph; rows a gate skips come back as zeros.  gnnd::uf_out(graph_id, x, gate?,
       ehat, rounds, status, nfull) mutates its four outputs and leaves the skipped rows as they were
+  gnnd::ufw(graph_id, x, llr?, scale, wmax, gate?, passthrough) -> (ehat, rounds, status, nfull,
+      events)   weighted union-find: uf with an edge's length its quantised reliability (llr, else
+      the priors in x); rows a gate skips come back as zeros.  gnnd::ufw_out mutates its five outputs
+  gnnd::belief_find(graph_id, x, iters, alpha, beta, early_stop, scale, wmax)
+      -> (ehat, status, iters_used, bp_status, pred, llr, rounds, nfull, events)   minsum, then ufw
+      on its posteriors for the codewords it left unsolved; gnnd::belief_find_out mutates its nine
 
 The single-codeword Tanner graph is a device object owned by libgnnd, not a tensor: ops
 take the integer id that `register_graph` hands out (TannerGraph does this on creation;
@@ -660,4 +666,96 @@ def uf_out(graph_id: int, x: Tensor, gate: Optional[Tensor], ehat: Tensor, round
 
 @uf_out.register_fake
 def _uf_out_fake(graph_id, x, gate, ehat, rounds, status, nfull):
+    return None
+
+
+# ---------------------------------------------------------------------------------------
+# weighted union-find and the one-call belief-find decoder
+# ---------------------------------------------------------------------------------------
+def _opt(t):
+    return None if t is None else t.contiguous()
+
+
+@torch.library.custom_op('gnnd::ufw', mutates_args=(), device_types='cuda')
+def ufw(graph_id: int, x: Tensor, llr: Optional[Tensor], scale: float, wmax: int,
+        gate: Optional[Tensor], passthrough: bool
+        ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from . import ops
+    g = graph_of(graph_id)
+    x = x.contiguous()
+    B = x.numel() // g.N
+    # zeros, not empty: the rows a gate skips are not written
+    ehat = torch.zeros(B * g.V, 1, dtype=x.dtype, device=x.device)
+    ints = tuple(torch.zeros(B, dtype=torch.int32, device=x.device) for _ in range(4))
+    ops._ufw_impl(g, x, _opt(llr), scale, wmax, _opt(gate), passthrough, ehat, *ints)
+    return (ehat,) + ints
+
+
+@ufw.register_fake
+def _ufw_fake(graph_id, x, llr, scale, wmax, gate, passthrough):
+    V, C, N, E = _DIMS[graph_id]
+    B = x.numel() // N
+    return (x.new_empty(B * V, 1),) + tuple(x.new_empty(B, dtype=torch.int32) for _ in range(4))
+
+
+@torch.library.custom_op('gnnd::ufw_out',
+                         mutates_args=('ehat', 'rounds', 'status', 'nfull', 'events'),
+                         device_types='cuda')
+def ufw_out(graph_id: int, x: Tensor, llr: Optional[Tensor], scale: float, wmax: int,
+            gate: Optional[Tensor], passthrough: bool, ehat: Tensor, rounds: Tensor,
+            status: Tensor, nfull: Tensor, events: Tensor) -> None:
+    from . import ops
+    ops._ufw_impl(graph_of(graph_id), x.contiguous(), _opt(llr), scale, wmax, _opt(gate),
+                  passthrough, ehat, rounds, status, nfull, events)
+
+
+@ufw_out.register_fake
+def _ufw_out_fake(graph_id, x, llr, scale, wmax, gate, passthrough, ehat, rounds, status, nfull,
+                  events):
+    return None
+
+
+@torch.library.custom_op('gnnd::belief_find', mutates_args=(), device_types='cuda')
+def belief_find(graph_id: int, x: Tensor, iters: int, alpha: float, beta: float, early_stop: bool,
+                scale: float, wmax: int
+                ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from . import ops
+    g = graph_of(graph_id)
+    x = x.contiguous()
+    B = x.numel() // g.N
+    ehat, pred, llr = (torch.empty(B * g.V, 1, dtype=x.dtype, device=x.device) for _ in range(3))
+    status, iters_used, bp_status, rounds, nfull, events = (
+        torch.empty(B, dtype=torch.int32, device=x.device) for _ in range(6))
+    ops._belief_find_impl(g, x, iters, alpha, beta, early_stop, scale, wmax, ehat, status,
+                          iters_used, bp_status, pred, llr, rounds, nfull, events)
+    return ehat, status, iters_used, bp_status, pred, llr, rounds, nfull, events
+
+
+@belief_find.register_fake
+def _belief_find_fake(graph_id, x, iters, alpha, beta, early_stop, scale, wmax):
+    V, C, N, E = _DIMS[graph_id]
+    B = x.numel() // N
+
+    def ints():
+        return x.new_empty(B, dtype=torch.int32)
+    return (x.new_empty(B * V, 1), ints(), ints(), ints(), x.new_empty(B * V, 1),
+            x.new_empty(B * V, 1), ints(), ints(), ints())
+
+
+@torch.library.custom_op('gnnd::belief_find_out',
+                         mutates_args=('ehat', 'status', 'iters_used', 'bp_status', 'pred', 'llr',
+                                       'rounds', 'nfull', 'events'), device_types='cuda')
+def belief_find_out(graph_id: int, x: Tensor, iters: int, alpha: float, beta: float,
+                    early_stop: bool, scale: float, wmax: int, ehat: Tensor, status: Tensor,
+                    iters_used: Tensor, bp_status: Tensor, pred: Tensor, llr: Tensor,
+                    rounds: Tensor, nfull: Tensor, events: Tensor) -> None:
+    from . import ops
+    ops._belief_find_impl(graph_of(graph_id), x.contiguous(), iters, alpha, beta, early_stop,
+                          scale, wmax, ehat, status, iters_used, bp_status, pred, llr, rounds,
+                          nfull, events)
+
+
+@belief_find_out.register_fake
+def _belief_find_out_fake(graph_id, x, iters, alpha, beta, early_stop, scale, wmax, ehat, status,
+                          iters_used, bp_status, pred, llr, rounds, nfull, events):
     return None

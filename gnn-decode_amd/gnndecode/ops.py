@@ -1403,6 +1403,214 @@ def matching_host(H):
 
 
 # ---------------------------------------------------------------------------------------
+# weighted union-find (gnnd_ufw) and the one-call belief-find decoder (gnnd_belief_find)
+# ---------------------------------------------------------------------------------------
+UFW_MAX_WEIGHT = 1024     # kGnndUfwMaxWeight
+
+
+def _ufw_check_params(scale, wmax):
+    scale = float(scale)
+    if not 0.0 <= scale < float('inf'):
+        raise ValueError(f'scale must be finite and >= 0, got {scale!r}')
+    if not isinstance(wmax, int) or isinstance(wmax, bool) or not 1 <= wmax <= UFW_MAX_WEIGHT:
+        raise ValueError(f'wmax must be an integer in [1, {UFW_MAX_WEIGHT}], got {wmax!r}')
+    return scale
+
+
+def ufw(graph, x, llr=None, scale=2.0, wmax=32, gate=None, passthrough=False, out=None):
+    """Weighted union-find, one HIP launch (gnnd_ufw, defined in include/gnnd.h): uf with the
+    length of edge v its quantised reliability, w = clamp(1 + trunc(r_v * scale), 1, wmax) with
+    r_v = llr [B*V(,1)] if given (the posteriors of minsum, relay_soft or bpgd: "belief-find"),
+    else the priors in x; a negative, zero or NaN reliability gives 1.  Clusters grow fast through
+    bits believed flipped and slowly through reliable ones.  -> (ehat, rounds, status, nfull,
+    events): as uf, rounds in unit half-steps, events [B] int32 the growth events (the jumps from
+    one filled edge to the next).  scale = 0 or wmax = 1 gives uf's bits.  gate [B] int32 as for
+    uf: codewords whose gate is 0 are skipped and none of their outputs written, so
+        ops.ufw(g, x, llr=llr, gate=status, out=(ehat, None, status, None, None))
+    finishes the codewords relay_soft or bpgd left unsolved, on the posteriors they stopped with.
+    passthrough=True (needs gate and llr) instead writes ehat = (llr < 0) and zero counters for
+    them.  Bit-reproducible (ufw_host gives the same bits).  The defaults scale = 2.0, wmax = 32
+    are not tuned: nobody has measured them against others beyond the grid of
+    tools/ufw_bench.py.  No host sync; `out` = the five tensors to write into, each but ehat may
+    be None to skip it (returned as None)."""
+    scale = _ufw_check_params(scale, wmax)
+    passthrough = bool(passthrough)
+    if passthrough and (gate is None or llr is None):
+        raise ValueError('passthrough needs gate and llr')
+    if torch.compiler.is_compiling():
+        if out is None:
+            return torch.ops.gnnd.ufw(graph.gid, x, llr, scale, wmax, gate, passthrough)
+        if len(out) != 5 or any(o is None for o in out):
+            raise ValueError('traced ufw needs out = (ehat, rounds, status, nfull, events)')
+        torch.ops.gnnd.ufw_out(graph.gid, x, llr, scale, wmax, gate, passthrough, *out)
+        return out
+    _require_gpu(x, llr, gate)
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f'ufw supports float32/float64, got {x.dtype}')
+    x = x.contiguous()
+    B = x.numel() // graph.N
+    if x.numel() != B * graph.N:
+        raise ValueError(f'x must hold B*N values (N = {graph.N})')
+    if llr is not None:
+        if llr.dtype != x.dtype:
+            raise TypeError(f'x ({x.dtype}) and llr ({llr.dtype}) must share a dtype')
+        llr = llr.contiguous()
+        if llr.numel() != B * graph.V:
+            raise ValueError(f'llr must hold B*V values (V = {graph.V})')
+    if gate is not None:
+        if gate.dtype != torch.int32:
+            raise TypeError(f'gate must be int32, got {gate.dtype}')
+        gate = gate.contiguous()
+        if gate.numel() != B:
+            raise ValueError(f'gate must hold B = {B} values')
+    if out is None:
+        out = ((torch.empty(B * graph.V, 1, dtype=x.dtype, device=x.device),)
+               + tuple(torch.empty(B, dtype=torch.int32, device=x.device) for _ in range(4)))
+    if len(out) != 5 or out[0] is None:
+        raise ValueError('out must be (ehat, rounds, status, nfull, events); only ehat is required')
+    _require_gpu(*out)
+    if out[0].dtype != x.dtype or out[0].numel() != B * graph.V or not out[0].is_contiguous():
+        raise ValueError(f'ehat must be contiguous {x.dtype} [{B * graph.V}]')
+    for t in out[1:]:
+        if t is not None and (t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
+            raise ValueError(f'rounds / status / nfull / events must be contiguous int32 [{B}]')
+    _ufw_impl(graph, x, llr, scale, wmax, gate, passthrough, *out)
+    return tuple(out)
+
+
+def _ufw_impl(graph, x, llr, scale, wmax, gate, passthrough, ehat, rounds, status, nfull, events):
+    """gnnd::ufw / gnnd::ufw_out implementation (gnndecode.library)."""
+    _lib.call('gnnd_ufw', graph.handle, dtype_code(x.dtype), _ptr(x), _ptr(llr), scale, wmax,
+              _ptr(gate), int(passthrough), _ptr(ehat), _ptr(rounds), _ptr(status), _ptr(nfull),
+              _ptr(events), x.numel() // graph.N, current_stream(x.device))
+
+
+def ufw_host(H, x, llr=None, scale=2.0, wmax=32, gate=None, passthrough=False):
+    """The host mirror of ufw (gnnd_ufw_host): numpy in, numpy out, no device.  H [V, C], x [B*N]
+    float32 or float64, llr [B*V] or None, gate [B] int32 or None -> (ehat like x's dtype [B*V],
+    rounds, status, nfull, events int32 [B]).  The rows a gate skips are returned as zeros."""
+    import numpy as np
+    scale = _ufw_check_params(scale, wmax)
+    if passthrough and (gate is None or llr is None):
+        raise ValueError('passthrough needs gate and llr')
+    V, C, var, chk, vp, cp = _host_graph(H)
+    x = np.ascontiguousarray(x)
+    if x.dtype not in (np.float32, np.float64):
+        raise TypeError(f'ufw_host supports float32/float64, got {x.dtype}')
+    B = x.size // (V + C)
+    if x.size != B * (V + C):
+        raise ValueError(f'x must hold B*N values (N = {V + C})')
+    if llr is not None:
+        llr = np.ascontiguousarray(llr, dtype=x.dtype)
+        if llr.size != B * V:
+            raise ValueError(f'llr must hold B*V values (V = {V})')
+    P32 = ctypes.POINTER(ctypes.c_int32)
+    if gate is not None:
+        gate = np.ascontiguousarray(gate, dtype=np.int32)
+        if gate.size != B:
+            raise ValueError(f'gate must hold B = {B} values')
+    ehat = np.zeros(B * V, x.dtype)
+    ints = [np.zeros(B, np.int32) for _ in range(4)]
+    _lib.call('gnnd_ufw_host', vp, cp, var.size, V, C,
+              _lib.F32 if x.dtype == np.float32 else _lib.F64, x.ctypes.data,
+              None if llr is None else llr.ctypes.data, scale, wmax,
+              None if gate is None else gate.ctypes.data_as(P32), int(bool(passthrough)),
+              ehat.ctypes.data, *(a.ctypes.data_as(P32) for a in ints), B)
+    return (ehat,) + tuple(ints)
+
+
+def belief_find(graph, x, iters, alpha=0.75, beta=0.0, early_stop=True, scale=2.0, wmax=32,
+                out=None):
+    """Belief-find in one call (gnnd_belief_find): minsum, then ufw on the min-sum posteriors with
+    the min-sum status as the gate and passthrough on, two launches on the current stream, no
+    workspace, no host sync.  `graph` must be matchable.  -> (ehat, status, iters_used, bp_status,
+    pred, llr, rounds, nfull, events): where bp_status is 0, ehat is min-sum's hard decision,
+    which satisfies the syndrome, and rounds / nfull / events are 0; elsewhere ehat / status /
+    rounds / nfull / events are ufw's.  Like bposd it always returns a syndrome-satisfying
+    estimate (on a graph whose components all have a virtual vertex, toric_code(L) is one), with
+    no elimination.  Everything but pred is bit-reproducible (belief_find_host gives the same
+    bits).  The defaults scale = 2.0, wmax = 32 are not tuned (see ufw).  `out`: the nine tensors
+    to write into; status, iters_used, rounds, nfull and events may be None to skip them."""
+    alpha, beta = _minsum_check_params(iters, alpha, beta)
+    early_stop = bool(early_stop)
+    scale = _ufw_check_params(scale, wmax)
+    if torch.compiler.is_compiling():
+        if out is None:
+            return torch.ops.gnnd.belief_find(graph.gid, x, iters, alpha, beta, early_stop, scale,
+                                              wmax)
+        if len(out) != 9 or any(o is None for o in out):
+            raise ValueError('traced belief_find needs all nine out tensors')
+        torch.ops.gnnd.belief_find_out(graph.gid, x, iters, alpha, beta, early_stop, scale, wmax,
+                                       *out)
+        return out
+    _require_gpu(x)
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f'belief_find supports float32/float64, got {x.dtype}')
+    x = x.contiguous()
+    B = x.numel() // graph.N
+    if x.numel() != B * graph.N:
+        raise ValueError(f'x must hold B*N values (N = {graph.N})')
+    if out is None:
+        def real():
+            return torch.empty(B * graph.V, 1, dtype=x.dtype, device=x.device)
+
+        def ints():
+            return torch.empty(B, dtype=torch.int32, device=x.device)
+        out = (real(), ints(), ints(), ints(), real(), real(), ints(), ints(), ints())
+    if len(out) != 9:
+        raise ValueError('out must be (ehat, status, iters_used, bp_status, pred, llr, rounds, '
+                         'nfull, events)')
+    ehat, status, iters_used, bp_status, pred, llr, rounds, nfull, events = out
+    if any(t is None for t in (ehat, bp_status, pred, llr)):
+        raise ValueError('ehat, bp_status, pred and llr are required in out')
+    _require_gpu(*out)
+    for t in (ehat, pred, llr):
+        if t.dtype != x.dtype or t.numel() != B * graph.V or not t.is_contiguous():
+            raise ValueError(f'ehat / pred / llr must be contiguous {x.dtype} [{B * graph.V}]')
+    for t in (status, iters_used, bp_status, rounds, nfull, events):
+        if t is not None and (t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
+            raise ValueError('status / iters_used / bp_status / rounds / nfull / events must be '
+                             f'contiguous int32 [{B}]')
+    _belief_find_impl(graph, x, iters, alpha, beta, early_stop, scale, wmax, *out)
+    return tuple(out)
+
+
+def _belief_find_impl(graph, x, iters, alpha, beta, early_stop, scale, wmax, ehat, status,
+                      iters_used, bp_status, pred, llr, rounds, nfull, events):
+    """gnnd::belief_find / gnnd::belief_find_out implementation (gnndecode.library)."""
+    _lib.call('gnnd_belief_find', graph.handle, dtype_code(x.dtype), _ptr(x), alpha, beta, iters,
+              int(early_stop), scale, wmax, _ptr(pred), _ptr(llr), _ptr(iters_used),
+              _ptr(bp_status), _ptr(ehat), _ptr(status), _ptr(rounds), _ptr(nfull), _ptr(events),
+              x.numel() // graph.N, current_stream(x.device))
+
+
+def belief_find_host(H, x, iters, alpha=0.75, beta=0.0, early_stop=True, scale=2.0, wmax=32):
+    """The host mirror of belief_find (gnnd_belief_find_host): numpy in, numpy out, no device.
+    -> (ehat, status, iters_used, bp_status, pred, llr, rounds, nfull, events)."""
+    import numpy as np
+    alpha, beta = _minsum_check_params(iters, alpha, beta)
+    scale = _ufw_check_params(scale, wmax)
+    V, C, var, chk, vp, cp = _host_graph(H)
+    x = np.ascontiguousarray(x)
+    if x.dtype not in (np.float32, np.float64):
+        raise TypeError(f'belief_find_host supports float32/float64, got {x.dtype}')
+    B = x.size // (V + C)
+    if x.size != B * (V + C):
+        raise ValueError(f'x must hold B*N values (N = {V + C})')
+    ehat, pred, llr = (np.empty(B * V, x.dtype) for _ in range(3))
+    status, iters_used, bp_status, rounds, nfull, events = (np.empty(B, np.int32)
+                                                            for _ in range(6))
+    P32 = ctypes.POINTER(ctypes.c_int32)
+    _lib.call('gnnd_belief_find_host', vp, cp, var.size, V, C,
+              _lib.F32 if x.dtype == np.float32 else _lib.F64, x.ctypes.data, alpha, beta, iters,
+              int(bool(early_stop)), scale, wmax, pred.ctypes.data, llr.ctypes.data,
+              iters_used.ctypes.data_as(P32), bp_status.ctypes.data_as(P32), ehat.ctypes.data,
+              status.ctypes.data_as(P32), rounds.ctypes.data_as(P32), nfull.ctypes.data_as(P32),
+              events.ctypes.data_as(P32), B)
+    return ehat, status, iters_used, bp_status, pred, llr, rounds, nfull, events
+
+
+# ---------------------------------------------------------------------------------------
 # gated OSD (gnnd_osd_gated) and the one-call BP+OSD decoder (gnnd_bposd)
 # ---------------------------------------------------------------------------------------
 def osd_gated_workspace(B):

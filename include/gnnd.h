@@ -918,7 +918,94 @@ int gnnd_uf_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges, 
                  int32_t num_chk, int dtype, const void* h_x, const int32_t* h_gate, void* h_ehat,
                  int32_t* h_rounds, int32_t* h_status, int32_t* h_nfull, int64_t batch);
 
-/* Adam (torch.optim.Adam update order, amsgrad/maximize off) on one flat parameter buffer of
+/* ---- weighted union-find and the one-call belief-find decoder --------------------------------
+ * gnnd_ufw is gnnd_uf with an edge's length its quantised reliability instead of 1 for every edge:
+ * clusters grow fast through bits believed flipped and slowly through reliable ones.  Fed the
+ * posteriors of a BP decoder it is "belief-find".  The graphs, the decoding graph
+ * (gnnd_graph_matching) and the refusals are gnnd_uf's.  Per codeword b, T = float / double:
+ *   reliability  r_v = d_llr[b*V + v] if d_llr is not NULL, else the prior x[b*N + v]; the sign
+ *                convention is min-sum's, positive = the bit is believed 0
+ *   weight       s = (T)scale, rounded once;  m = r_v * s, one multiply in T
+ *                w_v = wmax          if m >= (T)(wmax - 1)
+ *                w_v = 1 + (int)m    else if m > 0         (truncation; 1 <= w_v <= wmax - 1)
+ *                w_v = 1             otherwise
+ *                a NaN, a negative or zero reliability and inf * 0 all compare false and give 1;
+ *                +inf with scale > 0 gives wmax
+ *                len_v = 2 w_v half-units
+ *   set-up       defect[u], the virtual vertices, label[u] = u as in gnnd_uf;  grow[v] = 0;
+ *                rounds = events = status = 0
+ *   growth event:
+ *     odd[l] as in gnnd_uf; if no l is odd: growth ends
+ *     rate_v = odd[label[a_v]] + odd[label[b_v]]
+ *     edge v is active if rate_v > 0 and grow[v] < len_v
+ *     if no edge is active: status = 1, growth ends (the unsatisfiable component of gnnd_uf)
+ *     d = min over the active v of ceil((len_v - grow[v]) / rate_v)
+ *     every edge v: grow[v] = min(len_v, grow[v] + rate_v d), all edges from the same labels
+ *     rounds += d;  events += 1
+ *     labels: the fixed point of label[u] <- max over the edges with grow[v] == len_v
+ *   forest, parent edges, peel: gnnd_uf's, word for word, with "full" meaning grow[v] == len_v
+ * A jump of d is d unit steps (every edge grows rate_v half-units per step) between which no edge
+ * fills, so no label and no parity can change between them: the definition is the unit-step one,
+ * and rounds counts unit steps.  Every event fills at least one edge: events <= V, rounds <=
+ * 2 wmax V, no round limit.
+ * Anchor: with scale = 0 every w_v is 1, and d_ehat, d_rounds, d_status and d_nfull are bit for bit
+ * gnnd_uf's; so they are with wmax = 1.
+ * Outputs: d_ehat [B*V] in dtype, exactly 0.0 / 1.0, required; d_rounds, d_status, d_nfull as for
+ * gnnd_uf; d_events [B] int32 the growth events.  The last four may be NULL.
+ * Gate: d_gate [B] int32 may be NULL.  passthrough == 0: as gnnd_uf, a codeword whose gate is 0 is
+ * skipped and none of its outputs is written.  passthrough == 1 (needs d_gate and d_llr): such a
+ * codeword gets ehat_v = (d_llr[b*V + v] < 0) as exactly 0.0 / 1.0, false for -0.0 and a NaN (the
+ * pass-through of gnnd_osd_gated), and status = rounds = nfull = events = 0; its syndrome is not
+ * re-checked, the gate is the caller's claim.
+ * Guarantees: gnnd_uf's.  Where d_status[b] == 0 of a decoded codeword, d_ehat of b satisfies the
+ * syndrome exactly, for any x and any llr (a NaN or an infinity only changes a weight).  All
+ * outputs are bit-reproducible and equal to the host mirror's, in GNND_F32 and GNND_F64: the
+ * weight is one multiply and two compares in T, everything after it integers, each step an XOR, a
+ * min, or the unique fixed point of a monotone sweep (order free).
+ * Kernel: one launch on `stream`, one wave per codeword, no host sync (capturable).  The tile is
+ * gnnd_uf's (V + 4 N) int32 with the length that remains, len_v - grow[v], in the edge array (full
+ * is 0); the weights are computed by the wave from global memory at set-up.
+ * scale not finite or < 0, wmax outside [1, 1024] (rounds stays inside int32 for V <= 65535),
+ * passthrough not 0 / 1, passthrough == 1 without d_gate or d_llr, a NULL g, d_x or d_ehat, a dtype
+ * outside the enum: GNND_ERR_INVALID_ARG.  GNND_BF16, a graph that is not matchable, or a tile over
+ * 64 KiB: GNND_ERR_UNSUPPORTED.  All decided before any device call, nothing launched.  batch 0
+ * returns GNND_OK.  gnnd_ufw_host is the host mirror (no device, no tile limit): the same
+ * definition, the same refusals, the same bits in every output.
+ *
+ * gnnd_belief_find is gnnd_minsum(d_x, alpha, beta, iters, early_stop -> d_pred, d_llr, d_iters,
+ * d_bp_status) followed by gnnd_ufw(d_x, d_llr, scale, wmax, gate = d_bp_status, passthrough = 1
+ * -> d_ehat, d_rounds, d_status, d_nfull, d_events) on the same stream: two launches, no
+ * workspace, no host sync (capturable).  d_pred, d_llr, d_bp_status and d_ehat are required; the
+ * rest may be NULL.  Where d_bp_status[b] == 0, d_ehat of b is min-sum's own hard decision, which
+ * satisfies the syndrome, and rounds = nfull = events = 0; elsewhere it is gnnd_ufw's estimate on
+ * the posteriors min-sum stopped with.  On a matchable graph whose components all have a virtual
+ * vertex d_ehat satisfies the syndrome for every codeword.  Every output but d_pred is
+ * bit-reproducible and equal to the mirror's in both dtypes (d_pred as for gnnd_bposd: the
+ * mirror's bits in GNND_F64).  Every GNND_ERR_INVALID_ARG of either stage is decided before the
+ * first device call; GNND_ERR_UNSUPPORTED is the union of both stages' conditions, with nothing
+ * launched; batch 0 returns GNND_OK.  gnnd_belief_find_host is the host mirror.               */
+int gnnd_ufw(const gnnd_graph* g, int dtype, const void* d_x, const void* d_llr, double scale,
+             int32_t wmax, const int32_t* d_gate, int32_t passthrough, void* d_ehat,
+             int32_t* d_rounds, int32_t* d_status, int32_t* d_nfull, int32_t* d_events,
+             int64_t batch, void* stream);
+int gnnd_ufw_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges, int32_t num_var,
+                  int32_t num_chk, int dtype, const void* h_x, const void* h_llr, double scale,
+                  int32_t wmax, const int32_t* h_gate, int32_t passthrough, void* h_ehat,
+                  int32_t* h_rounds, int32_t* h_status, int32_t* h_nfull, int32_t* h_events,
+                  int64_t batch);
+int gnnd_belief_find(const gnnd_graph* g, int dtype, const void* d_x, double alpha, double beta,
+                     int32_t iters, int32_t early_stop, double scale, int32_t wmax, void* d_pred,
+                     void* d_llr, int32_t* d_iters, int32_t* d_bp_status, void* d_ehat,
+                     int32_t* d_status, int32_t* d_rounds, int32_t* d_nfull, int32_t* d_events,
+                     int64_t batch, void* stream);
+int gnnd_belief_find_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                          int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                          double alpha, double beta, int32_t iters, int32_t early_stop,
+                          double scale, int32_t wmax, void* h_pred, void* h_llr, int32_t* h_iters,
+                          int32_t* h_bp_status, void* h_ehat, int32_t* h_status,
+                          int32_t* h_rounds, int32_t* h_nfull, int32_t* h_events, int64_t batch);
+
+/* Adam(torch.optim.Adam update order, amsgrad/maximize off) on one flat parameter buffer of
  * n values with its two moment buffers; *d_step is the device-resident step count (double,
  * incremented by the call), so a whole training step with the update can be captured in one
  * HIP graph.  Single-workgroup kernel (sized for the decoders' ~10^3 parameters).          */
