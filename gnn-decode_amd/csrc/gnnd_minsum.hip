@@ -8,6 +8,7 @@
 #include "gnnd_minsum_host.h"
 #include "gnnd_bposd_host.h"
 #include "gnnd_ufw_host.h"
+#include "gnnd_lsd_host.h"
 
 // this translation unit's debug word: gnnd_debug_take_minsum() (the collector list of
 // gnnd_debug_flags lives in the decoder's translation unit, which this feature leaves alone;
@@ -182,6 +183,51 @@ extern "C" int gnnd_bposd_host(const int64_t* h_var, const int64_t* h_chk, int64
     return gnnd_bposd_host_checked(h_var, h_chk, num_edges, num_var, num_chk, dtype, h_x, alpha,
                                    beta, iters, early_stop, base, method, order, h_pred, h_llr,
                                    h_iters, h_bp_status, h_ehat, h_status, h_choice, batch);
+}
+
+// ---------------------------------------------------------------------------------------
+// gnnd_bplsd: gnnd_bposd with gnnd_lsd_gated as its second stage.  Every refusal of either stage is
+// decided here, before the first launch.
+// ---------------------------------------------------------------------------------------
+bool gnnd_lsd_fits(const gnnd_graph* g, size_t elem);      // gnnd_lsd.hip: the LDS limits of gnnd_lsd
+
+extern "C" int gnnd_bplsd(const gnnd_graph* g, int dtype, const void* d_x, double alpha,
+                          double beta, int32_t iters, int32_t early_stop, int base,
+                          int32_t bits_per_step, void* d_pred, void* d_llr, int32_t* d_iters,
+                          int32_t* d_bp_status, void* d_ehat, int32_t* d_status,
+                          int32_t* d_rounds, int32_t* d_nclus, int32_t* d_ncols, void* d_work,
+                          int64_t work_bytes, int64_t batch, void* stream) {
+    const int rc = gnnd_args_rc(
+        g && batch >= 0 && gnnd_bplsd_params_ok(alpha, beta, iters, early_stop, base, bits_per_step),
+        dtype);
+    if (rc != GNND_OK) return rc;
+    if (batch == 0) return GNND_OK;
+    if (!d_x || !d_pred || !d_llr || !d_bp_status || !d_ehat || !d_work)
+        return GNND_ERR_INVALID_ARG;
+    if (batch > kOsdGatedMaxBatch) return GNND_ERR_UNSUPPORTED;
+    if (work_bytes < gnnd_osd_gated_bytes(batch)) return GNND_ERR_INVALID_ARG;
+    const size_t elem = dtype == GNND_F32 ? sizeof(float) : sizeof(double);
+    if (g->min_dc < 2 || minsum_plan(g->view.V, g->view.E, elem).waves == 0 ||
+        !gnnd_lsd_fits(g, elem))
+        return GNND_ERR_UNSUPPORTED;
+    const int st = gnnd_minsum(g, dtype, d_x, alpha, beta, iters, early_stop, d_pred, d_llr,
+                               d_iters, d_bp_status, batch, stream);
+    if (st != GNND_OK) return st;
+    return gnnd_lsd_gated(g, dtype, d_x, d_pred, d_llr, d_bp_status, base, bits_per_step, d_ehat,
+                          d_status, d_rounds, d_nclus, d_ncols, d_work, work_bytes, batch, stream);
+}
+
+extern "C" int gnnd_bplsd_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                               int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                               double alpha, double beta, int32_t iters, int32_t early_stop,
+                               int base, int32_t bits_per_step, void* h_pred, void* h_llr,
+                               int32_t* h_iters, int32_t* h_bp_status, void* h_ehat,
+                               int32_t* h_status, int32_t* h_rounds, int32_t* h_nclus,
+                               int32_t* h_ncols, int64_t batch) {
+    return gnnd_bplsd_host_checked(h_var, h_chk, num_edges, num_var, num_chk, dtype, h_x, alpha,
+                                   beta, iters, early_stop, base, bits_per_step, h_pred, h_llr,
+                                   h_iters, h_bp_status, h_ehat, h_status, h_rounds, h_nclus,
+                                   h_ncols, batch);
 }
 
 // ---------------------------------------------------------------------------------------

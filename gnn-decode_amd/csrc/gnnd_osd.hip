@@ -4,11 +4,13 @@
 #include "gnnd_common.h"
 #include "gnnd_wave_tile.h"
 #include "gnnd_osd_host.h"
+#include "gnnd_osd_tile.h"
 
 GNND_DEBUG_TU(osd)
 
 // ---------------------------------------------------------------------------------------
-// The wave-private-tile plan of gnnd_wave_tile.h.  Per codeword:
+// The wave-private-tile plan of gnnd_wave_tile.h with the tile and the shared steps of
+// gnnd_osd_tile.h (phases 1-3, which gnnd_lsd.hip runs too).  Per codeword:
 //   1. keys into LDS; every lane ranks its variables by counting (rank(v) = #{u : key_u > key_v
 //      or (key_u == key_v and u < v)}: a permutation, O(V^2 / 64) compares per lane) and scatters
 //      v to order[rank];
@@ -35,137 +37,6 @@ GNND_DEBUG_TU(osd)
 //   7. e is written once, for the chosen candidate: its free columns and the pivots of the rows
 //      its mask leaves set.
 // ---------------------------------------------------------------------------------------
-constexpr int kOsdMaxRowsPerLane = 32;      // `used` is one 32-bit mask per lane: C <= 2048
-
-struct OsdPlan {
-    int words;        // column words per row, ceil(V / 32)
-    int stride;       // words per row in LDS (columns + syndrome word, odd)
-    int rpl;          // rows per lane, ceil(C / 64)
-    int off_key, off_order, off_piv, off_e;   // byte offsets inside one wave's tile
-    int wave_bytes;   // one wave's tile (16-byte multiple)
-    int waves;        // waves per workgroup (0: the matrix does not fit)
-};
-
-static OsdPlan osd_plan(int V, int C, size_t elem) {
-    OsdPlan p;
-    p.words = (V + 31) / 32;
-    p.stride = (p.words + 1) | 1;
-    p.rpl = (C + 63) / 64;
-    const size_t a = (size_t)C * p.stride * 4;
-    // V, C <= 65535 and a is clamped to the limit: every offset fits an int
-    p.off_key = (int)wave_tile_align16(a > kWaveTileLdsLimit ? kWaveTileLdsLimit : a);
-    p.off_order = p.off_key + (int)wave_tile_align16((size_t)V * elem);
-    p.off_piv = p.off_order + (int)wave_tile_align16((size_t)V * 2);
-    p.off_e = p.off_piv + (int)wave_tile_align16((size_t)C * 2);
-    p.wave_bytes = p.off_e + (int)wave_tile_align16((size_t)V);
-    p.waves = a <= kWaveTileLdsLimit && p.rpl <= kOsdMaxRowsPerLane
-                  ? wave_tile_waves((size_t)p.wave_bytes) : 0;
-    return p;
-}
-
-// one wave's tile
-template <typename T>
-struct OsdTile {
-    uint32_t* A;
-    T* key;
-    uint16_t* order;
-    uint16_t* piv;
-    uint8_t* e;
-    __device__ __forceinline__ OsdTile(char* tile, const OsdPlan& pl)
-        : A((uint32_t*)tile), key((T*)(tile + pl.off_key)),
-          order((uint16_t*)(tile + pl.off_order)), piv((uint16_t*)(tile + pl.off_piv)),
-          e((uint8_t*)(tile + pl.off_e)) {}
-};
-
-// ---- phase 1: base vector, ordering key, column order by counting ----
-template <typename T>
-__device__ __forceinline__ void osd_keys_and_order(const OsdTile<T>& t, int V, int hard,
-                                                   const T* __restrict__ pb, int lane) {
-    for (int v = lane; v < V; v += 64) {
-        const T p = pb[v];
-        const T d = p - T(0.5);
-        const T k = hard ? -g_abs(d) : p;
-        t.key[v] = p != p ? -(T)INFINITY : k;
-        t.e[v] = (uint8_t)(hard && p > T(0.5));
-    }
-    wave_tile_sync();
-    for (int v = lane; v < V; v += 64) {
-        const T kv = t.key[v];
-        int rank = 0;
-        for (int u = 0; u < V; ++u) {
-            const T ku = t.key[u];
-            rank += (ku > kv) | ((ku == kv) & (u < v));
-        }
-        t.order[GNND_DIDX(rank, V, GNND_DBG_LDS_POS)] = (uint16_t)v;
-    }
-}
-
-// ---- phase 2: A = H^T rows with the residual syndrome ----
-template <typename T>
-__device__ __forceinline__ void osd_build_rows(const OsdTile<T>& t, const GraphView& g,
-                                               const OsdPlan& pl, const T* __restrict__ xchk,
-                                               int lane) {
-    const int C = g.C, S = pl.stride, syn = pl.words;
-    for (int k = 0; k < pl.rpl; ++k) {
-        const int r = lane + 64 * k;
-        if (r >= C) break;
-        uint32_t* row = t.A + (size_t)r * S;
-        for (int w = 0; w < S; ++w) row[w] = 0;
-        int par = xchk[r] < T(0);
-        for (int i = g.chk_ptr[r]; i < g.chk_ptr[r + 1]; ++i) {
-            const int e = GNND_DIDX(g.chk_edge[GNND_DIDX(i, g.E, GNND_DBG_SLOT)], g.E, GNND_DBG_SLOT);
-            const int v = GNND_DIDX((int)(g.edge_vc[e] & 0xffffu), g.V, GNND_DBG_VAR);
-            row[v >> 5] |= 1u << (v & 31);
-            par ^= t.e[v];
-        }
-        row[syn] = (uint32_t)par;
-    }
-    wave_tile_sync();
-}
-
-// ---- phase 3: Gauss-Jordan over the ordered columns; returns the lane's pivot-row mask
-// (bit k: row lane + 64 k is a pivot row) ----
-template <typename T>
-__device__ __forceinline__ uint32_t osd_eliminate(const OsdTile<T>& t, const OsdPlan& pl, int V,
-                                                  int C, int lane) {
-    const int S = pl.stride;
-    uint32_t* A = t.A;
-    uint32_t used = 0;
-    int rank = 0;
-    for (int pos = 0; pos < V && rank < C; ++pos) {
-        const int j = GNND_DIDX((int)t.order[pos], V, GNND_DBG_VAR);
-        const int wj = j >> 5;
-        const uint32_t bj = 1u << (j & 31);
-        uint32_t hit = 0;               // bit k: row lane + 64 k holds column j
-        int prow = -1;
-        for (int k = 0; k < pl.rpl; ++k) {
-            const int r = lane + 64 * k;
-            const bool has = r < C && (A[(size_t)r * S + wj] & bj);
-            hit |= (uint32_t)has << k;
-            if (prow < 0) {
-                const unsigned long long m = __ballot(has && !((used >> k) & 1u));
-                if (m) prow = 64 * k + __builtin_ctzll(m);
-            }
-        }
-        if (prow < 0) continue;
-        GNND_DCHECK(prow < C, GNND_DBG_NODE);
-        if (lane == (prow & 63)) {
-            used |= 1u << (prow >> 6);
-            hit &= ~(1u << (prow >> 6));
-            t.piv[prow] = (uint16_t)j;
-        }
-        ++rank;
-        const uint32_t* prw = A + (size_t)prow * S;
-        for (int w = 0; w < S; ++w) {
-            const uint32_t pw = __builtin_amdgcn_readfirstlane(prw[w]);
-            if (pw == 0) continue;
-            for (int k = 0; k < pl.rpl; ++k)
-                if ((hit >> k) & 1u) A[(size_t)(lane + 64 * k) * S + w] ^= pw;
-        }
-        wave_tile_sync();
-    }
-    return used;
-}
 
 template <typename T>
 __global__ void __launch_bounds__(256)
@@ -372,96 +243,12 @@ osd_kernel(GraphView g, OsdPlan pl, int hard, int method, int order, const T* __
 // gated OSD (gnnd_osd_gated): only the codewords with gate != 0 are eliminated.  The host does not
 // know how many there are, so two launches share the caller's scratch, int32 count then int32
 // list[B]:
-//   osd_gate_kernel   workgroup 0 strides over the gate and writes the ascending list of gated
-//                     codewords and their count: per chunk of 4096 every lane owns four
-//                     consecutive codewords, one __ballot per item gives the prefix inside the
-//                     wave, the 16 wave totals cross the workgroup through LDS (two buffers: one
-//                     barrier per chunk), the running base stays in a register.  No atomics, so
-//                     no counter to clear.  The other workgroups write the pass-through outputs
-//                     of the ungated codewords, 64 codewords per workgroup step, consecutive
-//                     lanes on consecutive elements;
+//   osd_gate_kernel   (gnnd_osd_tile.h) the ascending list of gated codewords and their count, and
+//                     the pass-through outputs of the ungated ones: status 0, choice -1;
 //   osd_gated_kernel  osd_kernel's plan and grid (the worst case); wave w takes list entries
 //                     w, w + (waves in flight), ... below the count it reads from the scratch and
 //                     runs osd_codeword on list[i].  With count 0 every wave leaves at once.
 // ---------------------------------------------------------------------------------------
-constexpr int kGateThreads = 1024;          // 16 waves
-constexpr int kGatePerLane = 4;
-constexpr int kGateChunk = kGateThreads * kGatePerLane;
-constexpr int kGateRows = 64;               // codewords per pass-through step of a workgroup
-constexpr int64_t kGateMaxBlocks = 2048;
-
-template <typename T>
-__global__ void __launch_bounds__(kGateThreads)
-osd_gate_kernel(int V, const int32_t* __restrict__ gate, const T* __restrict__ pred,
-                const T* __restrict__ llr, T* __restrict__ ehat, int32_t* __restrict__ status,
-                int32_t* __restrict__ choice, int32_t* __restrict__ work, int64_t B) {
-    if (blockIdx.x == 0) {
-        // ---- compaction ----
-        __shared__ int s_tot[2][kGateThreads / 64];
-        int32_t* list = work + 1;
-        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-        const unsigned long long below = (1ull << lane) - 1;
-        int base = 0;                       // gated codewords before the chunk, workgroup-uniform
-        int gv[kGatePerLane];               // the chunk's gates, loaded one chunk ahead
-#pragma unroll
-        for (int j = 0; j < kGatePerLane; ++j) {
-            const int64_t b = (int64_t)threadIdx.x * kGatePerLane + j;
-            gv[j] = b < B ? gate[b] : 0;
-        }
-        int buf = 0;
-        for (int64_t c0 = 0; c0 < B; c0 += kGateChunk, buf ^= 1) {
-            const int64_t b0 = c0 + (int64_t)threadIdx.x * kGatePerLane;
-            bool f[kGatePerLane];
-#pragma unroll
-            for (int j = 0; j < kGatePerLane; ++j) f[j] = gv[j] != 0;
-#pragma unroll
-            for (int j = 0; j < kGatePerLane; ++j) {
-                const int64_t b = b0 + kGateChunk + j;
-                gv[j] = b < B ? gate[b] : 0;
-            }
-            int before = 0, wtot = 0;       // set items of the lower lanes / of the wave
-#pragma unroll
-            for (int j = 0; j < kGatePerLane; ++j) {
-                const unsigned long long m = __ballot(f[j]);
-                before += __popcll(m & below);
-                wtot += __popcll(m);
-            }
-            if (lane == 0) s_tot[buf][wave] = wtot;
-            __syncthreads();
-            int wbase = 0, tot = 0;
-            for (int w = 0; w < kGateThreads / 64; ++w) {
-                const int n = s_tot[buf][w];
-                wbase += w < wave ? n : 0;
-                tot += n;
-            }
-            int pos = base + wbase + before;
-#pragma unroll
-            for (int j = 0; j < kGatePerLane; ++j)
-                if (f[j]) list[GNND_DIDX(pos++, (int)B, GNND_DBG_GRID)] = (int32_t)(b0 + j);
-            base += tot;
-        }
-        if (threadIdx.x == 0) work[0] = base;
-        return;
-    }
-    // ---- pass-through: the hard decision of the ungated codewords ----
-    for (int64_t g0 = (int64_t)(blockIdx.x - 1) * kGateRows; g0 < B;
-         g0 += (int64_t)(gridDim.x - 1) * kGateRows) {
-        const int rows = B - g0 < kGateRows ? (int)(B - g0) : kGateRows;
-        const unsigned n = (unsigned)rows * (unsigned)V;
-        for (unsigned i = threadIdx.x; i < n; i += kGateThreads) {
-            const unsigned r = i / (unsigned)V;
-            const int64_t b = g0 + r;
-            if (gate[b] != 0) continue;
-            const int64_t at = g0 * V + i;
-            const bool h = llr ? llr[at] < T(0) : pred[at] > T(0.5);
-            ehat[at] = h ? T(1) : T(0);
-            if (i == r * (unsigned)V) {
-                status[b] = 0;
-                if (choice) choice[b] = -1;
-            }
-        }
-    }
-}
 
 template <typename T>
 __global__ void __launch_bounds__(256)
@@ -565,10 +352,9 @@ static int launch_osd_gated(const gnnd_graph* g, const void* x, const void* pred
     const GraphView& v = g->view;
     const OsdPlan pl = osd_plan(v.V, v.C, sizeof(T));
     if (pl.waves == 0) return GNND_ERR_UNSUPPORTED;
-    const int64_t groups = (B + kGateRows - 1) / kGateRows;
-    const unsigned blocks = 1 + (unsigned)(groups < kGateMaxBlocks ? groups : kGateMaxBlocks);
-    osd_gate_kernel<T><<<blocks, kGateThreads, 0, st>>>(v.V, gate, (const T*)pred, (const T*)llr,
-                                                        (T*)ehat, status, choice, work, B);
+    const GateInts ints = {{status, choice, nullptr, nullptr}, {0, -1, 0, 0}};
+    osd_gate_kernel<T><<<osd_gate_blocks(B), kGateThreads, 0, st>>>(
+        v.V, gate, (const T*)pred, (const T*)llr, (T*)ehat, ints, work, B);
     GNND_LAUNCH_CHECK();
     osd_gated_kernel<T><<<wave_tile_blocks(B, pl.waves, pl.waves), 64 * pl.waves, (size_t)pl.waves * pl.wave_bytes, st>>>(
         v, pl, base == GNND_OSD_BASE_HARD, method, order, (const T*)x, (const T*)pred, (T*)ehat,

@@ -154,6 +154,18 @@ SIGNATURES = {
                                      ctypes.c_double, ctypes.c_double, _i32, _i32, ctypes.c_double,
                                      _i32, _vp, _vp, _c_i32p, _c_i32p, _vp, _c_i32p, _c_i32p,
                                      _c_i32p, _c_i32p, _i64]),
+    'gnnd_lsd': (_int, [_vp, _int, _vp, _vp, _int, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'gnnd_lsd_host': (_int, [_c_i64p, _c_i64p, _i64, _i32, _i32, _int, _vp, _vp, _int, _i32, _vp,
+                             _c_i32p, _c_i32p, _c_i32p, _c_i32p, _i64]),
+    'gnnd_lsd_gated': (_int, [_vp, _int, _vp, _vp, _vp, _vp, _int, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                              _i64, _i64, _vp]),
+    'gnnd_lsd_gated_host': (_int, [_c_i64p, _c_i64p, _i64, _i32, _i32, _int, _vp, _vp, _vp, _c_i32p,
+                                   _int, _i32, _vp, _c_i32p, _c_i32p, _c_i32p, _c_i32p, _i64]),
+    'gnnd_bplsd': (_int, [_vp, _int, _vp, ctypes.c_double, ctypes.c_double, _i32, _i32, _int, _i32,
+                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
+    'gnnd_bplsd_host': (_int, [_c_i64p, _c_i64p, _i64, _i32, _i32, _int, _vp, ctypes.c_double,
+                               ctypes.c_double, _i32, _i32, _int, _i32, _vp, _vp, _c_i32p, _c_i32p,
+                               _vp, _c_i32p, _c_i32p, _c_i32p, _c_i32p, _i64]),
     'gnnd_v24_check_mlp_table':(_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     'gnnd_adam_step': (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double,
                               ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp]),

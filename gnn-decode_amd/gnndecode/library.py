@@ -55,6 +55,14 @@ a custom op costs more than the 0.47 ms headline kernel, measured r02n):
   gnnd::belief_find(graph_id, x, iters, alpha, beta, early_stop, scale, wmax)
       -> (ehat, status, iters_used, bp_status, pred, llr, rounds, nfull, events)   minsum, then ufw
       on its posteriors for the codewords it left unsolved; gnnd::belief_find_out mutates its nine
+  gnnd::lsd(graph_id, x, pred, base, bits_per_step) -> (ehat, status, rounds, nclus, ncols)
+      localized-statistics decoding: clusters around the unsatisfied checks, each solved by osd0's
+      elimination over its own columns; gnnd::lsd_out mutates its five outputs
+  gnnd::lsd_gated(graph_id, x, pred, gate, base, bits_per_step, llr?) -> the same five, lsd on the
+      codewords with gate != 0, the hard decision passed through elsewhere; gnnd::lsd_gated_out
+  gnnd::bplsd(graph_id, x, iters, alpha, beta, early_stop, base, bits_per_step)
+      -> (ehat, status, rounds, nclus, ncols, iters_used, bp_status, pred, llr)   minsum, then
+      lsd_gated; gnnd::bplsd_out mutates its nine
 
 The single-codeword Tanner graph is a device object owned by libgnnd, not a tensor: ops
 take the integer id that `register_graph` hands out (TannerGraph does this on creation;
@@ -758,4 +766,130 @@ def belief_find_out(graph_id: int, x: Tensor, iters: int, alpha: float, beta: fl
 @belief_find_out.register_fake
 def _belief_find_out_fake(graph_id, x, iters, alpha, beta, early_stop, scale, wmax, ehat, status,
                           iters_used, bp_status, pred, llr, rounds, nfull, events):
+    return None
+
+
+# ---------------------------------------------------------------------------------------
+# localized-statistics decoding and the one-call BP+LSD decoder
+# ---------------------------------------------------------------------------------------
+def _lsd_new(pred, V):
+    pred = pred.contiguous()
+    B = pred.numel() // V
+    return pred, (torch.empty_like(pred),) + tuple(
+        torch.empty(B, dtype=torch.int32, device=pred.device) for _ in range(4))
+
+
+def _lsd_fake_outs(graph_id, pred):
+    B = pred.numel() // _DIMS[graph_id][0]
+    return (torch.empty_like(pred, memory_format=torch.contiguous_format),) + tuple(
+        pred.new_empty(B, dtype=torch.int32) for _ in range(4))
+
+
+@torch.library.custom_op('gnnd::lsd', mutates_args=(), device_types='cuda')
+def lsd(graph_id: int, x: Tensor, pred: Tensor, base: str, bits_per_step: int
+        ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from . import ops
+    g = graph_of(graph_id)
+    pred, out = _lsd_new(pred, g.V)
+    ops._lsd_impl(g, x.contiguous(), pred, base, bits_per_step, *out)
+    return out
+
+
+@lsd.register_fake
+def _lsd_fake(graph_id, x, pred, base, bits_per_step):
+    return _lsd_fake_outs(graph_id, pred)
+
+
+@torch.library.custom_op('gnnd::lsd_out',
+                         mutates_args=('ehat', 'status', 'rounds', 'nclus', 'ncols'),
+                         device_types='cuda')
+def lsd_out(graph_id: int, x: Tensor, pred: Tensor, base: str, bits_per_step: int, ehat: Tensor,
+            status: Tensor, rounds: Tensor, nclus: Tensor, ncols: Tensor) -> None:
+    from . import ops
+    ops._lsd_impl(graph_of(graph_id), x.contiguous(), pred.contiguous(), base, bits_per_step, ehat,
+                  status, rounds, nclus, ncols)
+
+
+@lsd_out.register_fake
+def _lsd_out_fake(graph_id, x, pred, base, bits_per_step, ehat, status, rounds, nclus, ncols):
+    return None
+
+
+@torch.library.custom_op('gnnd::lsd_gated', mutates_args=(), device_types='cuda')
+def lsd_gated(graph_id: int, x: Tensor, pred: Tensor, gate: Tensor, base: str, bits_per_step: int,
+              llr: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from . import ops
+    g = graph_of(graph_id)
+    pred, out = _lsd_new(pred, g.V)
+    ops._lsd_gated_impl(g, x.contiguous(), pred, gate.contiguous(), base, bits_per_step,
+                        None if llr is None else llr.contiguous(), *out)
+    return out
+
+
+@lsd_gated.register_fake
+def _lsd_gated_fake(graph_id, x, pred, gate, base, bits_per_step, llr):
+    return _lsd_fake_outs(graph_id, pred)
+
+
+@torch.library.custom_op('gnnd::lsd_gated_out',
+                         mutates_args=('ehat', 'status', 'rounds', 'nclus', 'ncols'),
+                         device_types='cuda')
+def lsd_gated_out(graph_id: int, x: Tensor, pred: Tensor, gate: Tensor, base: str,
+                  bits_per_step: int, llr: Optional[Tensor], ehat: Tensor, status: Tensor,
+                  rounds: Tensor, nclus: Tensor, ncols: Tensor) -> None:
+    from . import ops
+    ops._lsd_gated_impl(graph_of(graph_id), x.contiguous(), pred.contiguous(), gate.contiguous(),
+                        base, bits_per_step, None if llr is None else llr.contiguous(), ehat,
+                        status, rounds, nclus, ncols)
+
+
+@lsd_gated_out.register_fake
+def _lsd_gated_out_fake(graph_id, x, pred, gate, base, bits_per_step, llr, ehat, status, rounds,
+                        nclus, ncols):
+    return None
+
+
+@torch.library.custom_op('gnnd::bplsd', mutates_args=(), device_types='cuda')
+def bplsd(graph_id: int, x: Tensor, iters: int, alpha: float, beta: float, early_stop: bool,
+          base: str, bits_per_step: int
+          ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from . import ops
+    g = graph_of(graph_id)
+    x = x.contiguous()
+    B = x.numel() // g.N
+    ehat, pred, llr = (torch.empty(B * g.V, 1, dtype=x.dtype, device=x.device) for _ in range(3))
+    status, rounds, nclus, ncols, iters_used, bp_status = (
+        torch.empty(B, dtype=torch.int32, device=x.device) for _ in range(6))
+    ops._bplsd_impl(g, x, iters, alpha, beta, early_stop, base, bits_per_step, ehat, status, rounds,
+                    nclus, ncols, iters_used, bp_status, pred, llr)
+    return ehat, status, rounds, nclus, ncols, iters_used, bp_status, pred, llr
+
+
+@bplsd.register_fake
+def _bplsd_fake(graph_id, x, iters, alpha, beta, early_stop, base, bits_per_step):
+    V, C, N, E = _DIMS[graph_id]
+    B = x.numel() // N
+
+    def ints():
+        return x.new_empty(B, dtype=torch.int32)
+    return (x.new_empty(B * V, 1), ints(), ints(), ints(), ints(), ints(), ints(),
+            x.new_empty(B * V, 1), x.new_empty(B * V, 1))
+
+
+@torch.library.custom_op('gnnd::bplsd_out',
+                         mutates_args=('ehat', 'status', 'rounds', 'nclus', 'ncols', 'iters_used',
+                                       'bp_status', 'pred', 'llr'), device_types='cuda')
+def bplsd_out(graph_id: int, x: Tensor, iters: int, alpha: float, beta: float, early_stop: bool,
+              base: str, bits_per_step: int, ehat: Tensor, status: Tensor, rounds: Tensor,
+              nclus: Tensor, ncols: Tensor, iters_used: Tensor, bp_status: Tensor, pred: Tensor,
+              llr: Tensor) -> None:
+    from . import ops
+    ops._bplsd_impl(graph_of(graph_id), x.contiguous(), iters, alpha, beta, early_stop, base,
+                    bits_per_step, ehat, status, rounds, nclus, ncols, iters_used, bp_status, pred,
+                    llr)
+
+
+@bplsd_out.register_fake
+def _bplsd_out_fake(graph_id, x, iters, alpha, beta, early_stop, base, bits_per_step, ehat, status,
+                    rounds, nclus, ncols, iters_used, bp_status, pred, llr):
     return None

@@ -1836,6 +1836,269 @@ def bposd_host(H, x, iters, alpha=0.75, beta=0.0, early_stop=True, base='zero', 
     return ehat, status, choice, iters_used, bp_status, pred, llr
 
 
+# ---------------------------------------------------------------------------------------
+# localized-statistics decoding (gnnd_lsd, gnnd_lsd_gated) and the one-call BP+LSD decoder
+# (gnnd_bplsd)
+# ---------------------------------------------------------------------------------------
+def _lsd_check_params(base, bits_per_step):
+    if base not in _lib.OSD_BASE:
+        raise ValueError(f"base must be 'zero' or 'hard', got {base!r}")
+    if (not isinstance(bits_per_step, int) or isinstance(bits_per_step, bool)
+            or not 0 <= bits_per_step <= 2 ** 31 - 1):
+        raise ValueError(f'bits_per_step must be an integer in [0, 2^31 - 1], got {bits_per_step!r}')
+
+
+def _lsd_inputs(name, graph, x, pred, gate=None, llr=None, gated=False):
+    """The checks osd_gated makes of its inputs -> (x, pred, gate, llr, B), contiguous."""
+    _require_gpu(x, pred, gate, llr)
+    if x.dtype != pred.dtype or (llr is not None and llr.dtype != pred.dtype):
+        raise TypeError(f'x ({x.dtype}), pred ({pred.dtype}) and llr must share a dtype')
+    if pred.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f'{name} supports float32/float64, got {pred.dtype}')
+    x = x.contiguous()
+    pred = pred.contiguous()
+    B = pred.numel() // graph.V
+    if pred.numel() != B * graph.V or x.numel() != B * graph.N:
+        raise ValueError(f'pred must hold B*V and x B*N values (V = {graph.V}, N = {graph.N})')
+    if gated:
+        if gate.dtype != torch.int32:
+            raise TypeError(f'gate must be int32, got {gate.dtype}')
+        gate = gate.contiguous()
+        if gate.numel() != B:
+            raise ValueError('gate must hold B values')
+    if llr is not None:
+        llr = llr.contiguous()
+        if llr.numel() != pred.numel():
+            raise ValueError('llr must hold B*V values')
+    return x, pred, gate, llr, B
+
+
+def _lsd_outs(out, pred, B, V):
+    """(ehat, status, rounds, nclus, ncols) of the LSD calls; the four int outputs may be None."""
+    dtype = pred.dtype
+    if out is None:
+        out = (torch.empty_like(pred),) + tuple(
+            torch.empty(B, dtype=torch.int32, device=pred.device) for _ in range(4))
+    if len(out) != 5:
+        raise ValueError('out must be (ehat, status, rounds, nclus, ncols)')
+    if out[0] is None:
+        raise ValueError('ehat is required in out')
+    _require_gpu(*out)
+    if out[0].dtype != dtype or out[0].numel() != B * V or not out[0].is_contiguous():
+        raise ValueError(f'ehat must be contiguous {dtype} [{B * V}]')
+    for t in out[1:]:
+        if t is not None and (t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
+            raise ValueError(f'status / rounds / nclus / ncols must be contiguous int32 [{B}]')
+    return tuple(out)
+
+
+def lsd(graph, x, pred, base='zero', bits_per_step=1, out=None):
+    """Localized-statistics decoding of a decoder's soft output, one HIP launch (gnnd_lsd):
+    clusters grow around the unsatisfied checks, on any Tanner graph, and every round solves them
+    by osd0's elimination restricted to the cluster columns.  x, pred and base as for osd0.
+    bits_per_step = k > 0: every unsolved cluster takes its k most likely boundary variables per
+    round (1, the default, is the published LSD-0 rule); 0: its whole boundary.  -> (ehat, status,
+    rounds, nclus, ncols): status [B] is osd0's on every input, and where it is 0 ehat satisfies
+    the syndrome and is osd0's solution for the column order "cluster variables first"; rounds
+    [B] the growth rounds, nclus [B] the clusters and ncols [B] the cluster variables at the end.
+    All outputs are bit-reproducible in both dtypes (lsd_host gives the same bits).  No host
+    sync; `out`: the five tensors to write into, all but ehat may be None to skip them."""
+    _lsd_check_params(base, bits_per_step)
+    if torch.compiler.is_compiling():
+        if out is None:
+            return torch.ops.gnnd.lsd(graph.gid, x, pred, base, bits_per_step)
+        if len(out) != 5 or any(o is None for o in out):
+            raise ValueError('traced lsd needs all five out tensors')
+        torch.ops.gnnd.lsd_out(graph.gid, x, pred, base, bits_per_step, *out)
+        return out
+    x, pred, _, _, B = _lsd_inputs('lsd', graph, x, pred)
+    out = _lsd_outs(out, pred, B, graph.V)
+    _lsd_impl(graph, x, pred, base, bits_per_step, *out)
+    return out
+
+
+def _lsd_impl(graph, x, pred, base, bits_per_step, ehat, status, rounds, nclus, ncols):
+    """gnnd::lsd / gnnd::lsd_out implementation (gnndecode.library)."""
+    _lib.call('gnnd_lsd', graph.handle, dtype_code(pred.dtype), _ptr(x), _ptr(pred),
+              _lib.OSD_BASE[base], bits_per_step, _ptr(ehat), _ptr(status), _ptr(rounds),
+              _ptr(nclus), _ptr(ncols), pred.numel() // graph.V, current_stream(pred.device))
+
+
+def lsd_gated(graph, x, pred, gate, base='zero', bits_per_step=1, llr=None, out=None, work=None):
+    """lsd on the codewords a gate selects (gnnd_lsd_gated): gate, llr, the pass-through rule, the
+    two launches and `work` as for osd_gated.  Where gate != 0 the five outputs are bit for bit
+    lsd's; a pass-through codeword gets its hard decision and status = rounds = nclus = ncols =
+    0.  -> (ehat, status, rounds, nclus, ncols); `out` as for lsd."""
+    _lsd_check_params(base, bits_per_step)
+    if torch.compiler.is_compiling():
+        if out is None:
+            return torch.ops.gnnd.lsd_gated(graph.gid, x, pred, gate, base, bits_per_step, llr)
+        if len(out) != 5 or any(o is None for o in out):
+            raise ValueError('traced lsd_gated needs all five out tensors')
+        torch.ops.gnnd.lsd_gated_out(graph.gid, x, pred, gate, base, bits_per_step, llr, *out)
+        return out
+    x, pred, gate, llr, B = _lsd_inputs('lsd_gated', graph, x, pred, gate, llr, gated=True)
+    out = _lsd_outs(out, pred, B, graph.V)
+    _lsd_gated_impl(graph, x, pred, gate, base, bits_per_step, llr, *out, work=work)
+    return out
+
+
+def _lsd_gated_impl(graph, x, pred, gate, base, bits_per_step, llr, ehat, status, rounds, nclus,
+                    ncols, work=None):
+    """gnnd::lsd_gated / gnnd::lsd_gated_out implementation (gnndecode.library)."""
+    B = pred.numel() // graph.V
+    work, nbytes = _gated_work(work, B, pred.device)
+    _lib.call('gnnd_lsd_gated', graph.handle, dtype_code(pred.dtype), _ptr(x), _ptr(pred),
+              _ptr(llr), _ptr(gate), _lib.OSD_BASE[base], bits_per_step, _ptr(ehat), _ptr(status),
+              _ptr(rounds), _ptr(nclus), _ptr(ncols), _ptr(work), nbytes, B,
+              current_stream(pred.device))
+
+
+def bplsd(graph, x, iters, alpha=0.75, beta=0.0, early_stop=True, base='zero', bits_per_step=1,
+          out=None, work=None):
+    """The BP+LSD decoder in one call (gnnd_bplsd): minsum (flooding schedule), then lsd_gated with
+    the min-sum status as the gate and the min-sum llr as the pass-through decision, three
+    launches on the current stream, no host sync.  -> (ehat, status, rounds, nclus, ncols,
+    iters_used, bp_status, pred, llr): where bp_status is 0 ehat is min-sum's hard decision and
+    every output bposd shares is bposd's; elsewhere ehat / status / rounds / nclus / ncols are
+    lsd's.  Everything but pred is bit-reproducible (bplsd_host gives the same bits).  `out`: the
+    nine tensors to write into, status, rounds, nclus, ncols and iters_used may be None to skip
+    them; `work` as for osd_gated."""
+    alpha, beta = _minsum_check_params(iters, alpha, beta)
+    early_stop = bool(early_stop)
+    _lsd_check_params(base, bits_per_step)
+    if torch.compiler.is_compiling():
+        if out is None:
+            return torch.ops.gnnd.bplsd(graph.gid, x, iters, alpha, beta, early_stop, base,
+                                        bits_per_step)
+        if len(out) != 9 or any(o is None for o in out):
+            raise ValueError('traced bplsd needs all nine out tensors')
+        torch.ops.gnnd.bplsd_out(graph.gid, x, iters, alpha, beta, early_stop, base, bits_per_step,
+                                 *out)
+        return out
+    _require_gpu(x)
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f'bplsd supports float32/float64, got {x.dtype}')
+    x = x.contiguous()
+    B = x.numel() // graph.N
+    if x.numel() != B * graph.N:
+        raise ValueError(f'x must hold B*N values (N = {graph.N})')
+    if out is None:
+        def real():
+            return torch.empty(B * graph.V, 1, dtype=x.dtype, device=x.device)
+
+        def ints():
+            return torch.empty(B, dtype=torch.int32, device=x.device)
+        out = (real(), ints(), ints(), ints(), ints(), ints(), ints(), real(), real())
+    if len(out) != 9:
+        raise ValueError('out must be (ehat, status, rounds, nclus, ncols, iters_used, bp_status, '
+                         'pred, llr)')
+    ehat, status, rounds, nclus, ncols, iters_used, bp_status, pred, llr = out
+    if any(t is None for t in (ehat, bp_status, pred, llr)):
+        raise ValueError('ehat, bp_status, pred and llr are required in out')
+    _require_gpu(*out)
+    for t in (ehat, pred, llr):
+        if t.dtype != x.dtype or t.numel() != B * graph.V or not t.is_contiguous():
+            raise ValueError(f'ehat / pred / llr must be contiguous {x.dtype} [{B * graph.V}]')
+    for t in (status, rounds, nclus, ncols, iters_used, bp_status):
+        if t is not None and (t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
+            raise ValueError('status / rounds / nclus / ncols / iters_used / bp_status must be '
+                             f'contiguous int32 [{B}]')
+    _bplsd_impl(graph, x, iters, alpha, beta, early_stop, base, bits_per_step, *out, work=work)
+    return tuple(out)
+
+
+def _bplsd_impl(graph, x, iters, alpha, beta, early_stop, base, bits_per_step, ehat, status,
+                rounds, nclus, ncols, iters_used, bp_status, pred, llr, work=None):
+    """gnnd::bplsd / gnnd::bplsd_out implementation (gnndecode.library)."""
+    B = x.numel() // graph.N
+    work, nbytes = _gated_work(work, B, x.device)
+    _lib.call('gnnd_bplsd', graph.handle, dtype_code(x.dtype), _ptr(x), alpha, beta, iters,
+              int(early_stop), _lib.OSD_BASE[base], bits_per_step, _ptr(pred), _ptr(llr),
+              _ptr(iters_used), _ptr(bp_status), _ptr(ehat), _ptr(status), _ptr(rounds),
+              _ptr(nclus), _ptr(ncols), _ptr(work), nbytes, B, current_stream(x.device))
+
+
+def _lsd_host_inputs(name, H, x, pred, gate=None, llr=None, gated=False):
+    import numpy as np
+    V, C, var, chk, vp, cp = _host_graph(H)
+    pred = np.ascontiguousarray(pred)
+    if pred.dtype not in (np.float32, np.float64):
+        raise TypeError(f'{name} supports float32/float64, got {pred.dtype}')
+    x = np.ascontiguousarray(x, dtype=pred.dtype)
+    B = pred.size // V
+    if pred.size != B * V or x.size != B * (V + C):
+        raise ValueError(f'pred must hold B*V and x B*N values (V = {V}, N = {V + C})')
+    if gated:
+        gate = np.ascontiguousarray(gate, dtype=np.int32)
+        if gate.size != B:
+            raise ValueError('gate must hold B values')
+    if llr is not None:
+        llr = np.ascontiguousarray(llr, dtype=pred.dtype)
+        if llr.size != pred.size:
+            raise ValueError('llr must hold B*V values')
+    return V, C, var, vp, cp, x, pred, gate, llr, B
+
+
+def lsd_host(H, x, pred, base='zero', bits_per_step=1):
+    """The host mirror of lsd (gnnd_lsd_host): numpy in, numpy out, no device.  H [V, C], x [B*N],
+    pred [B*V] float32 or float64 -> (ehat like pred, status, rounds, nclus, ncols int32 [B])."""
+    import numpy as np
+    _lsd_check_params(base, bits_per_step)
+    V, C, var, vp, cp, x, pred, _, _, B = _lsd_host_inputs('lsd_host', H, x, pred)
+    ehat = np.empty_like(pred)
+    ints = tuple(np.empty(B, np.int32) for _ in range(4))
+    P32 = ctypes.POINTER(ctypes.c_int32)
+    _lib.call('gnnd_lsd_host', vp, cp, var.size, V, C,
+              _lib.F32 if pred.dtype == np.float32 else _lib.F64, x.ctypes.data, pred.ctypes.data,
+              _lib.OSD_BASE[base], bits_per_step, ehat.ctypes.data,
+              *(a.ctypes.data_as(P32) for a in ints), B)
+    return (ehat,) + ints
+
+
+def lsd_gated_host(H, x, pred, gate, base='zero', bits_per_step=1, llr=None):
+    """The host mirror of lsd_gated (gnnd_lsd_gated_host): numpy in, numpy out, no device.
+    -> (ehat like pred, status, rounds, nclus, ncols int32 [B])."""
+    import numpy as np
+    _lsd_check_params(base, bits_per_step)
+    V, C, var, vp, cp, x, pred, gate, llr, B = _lsd_host_inputs('lsd_gated_host', H, x, pred, gate,
+                                                                llr, gated=True)
+    ehat = np.empty_like(pred)
+    ints = tuple(np.empty(B, np.int32) for _ in range(4))
+    P32 = ctypes.POINTER(ctypes.c_int32)
+    _lib.call('gnnd_lsd_gated_host', vp, cp, var.size, V, C,
+              _lib.F32 if pred.dtype == np.float32 else _lib.F64, x.ctypes.data, pred.ctypes.data,
+              None if llr is None else llr.ctypes.data, gate.ctypes.data_as(P32),
+              _lib.OSD_BASE[base], bits_per_step, ehat.ctypes.data,
+              *(a.ctypes.data_as(P32) for a in ints), B)
+    return (ehat,) + ints
+
+
+def bplsd_host(H, x, iters, alpha=0.75, beta=0.0, early_stop=True, base='zero', bits_per_step=1):
+    """The host mirror of bplsd (gnnd_bplsd_host): numpy in, numpy out, no device.  -> (ehat,
+    status, rounds, nclus, ncols, iters_used, bp_status, pred, llr)."""
+    import numpy as np
+    alpha, beta = _minsum_check_params(iters, alpha, beta)
+    _lsd_check_params(base, bits_per_step)
+    V, C, var, chk, vp, cp = _host_graph(H)
+    x = np.ascontiguousarray(x)
+    if x.dtype not in (np.float32, np.float64):
+        raise TypeError(f'bplsd_host supports float32/float64, got {x.dtype}')
+    B = x.size // (V + C)
+    if x.size != B * (V + C):
+        raise ValueError(f'x must hold B*N values (N = {V + C})')
+    ehat, pred, llr = (np.empty(B * V, x.dtype) for _ in range(3))
+    status, rounds, nclus, ncols, iters_used, bp_status = (np.empty(B, np.int32) for _ in range(6))
+    P32 = ctypes.POINTER(ctypes.c_int32)
+    _lib.call('gnnd_bplsd_host', vp, cp, var.size, V, C,
+              _lib.F32 if x.dtype == np.float32 else _lib.F64, x.ctypes.data, alpha, beta, iters,
+              int(bool(early_stop)), _lib.OSD_BASE[base], bits_per_step, pred.ctypes.data,
+              llr.ctypes.data, iters_used.ctypes.data_as(P32), bp_status.ctypes.data_as(P32),
+              ehat.ctypes.data, status.ctypes.data_as(P32), rounds.ctypes.data_as(P32),
+              nclus.ctypes.data_as(P32), ncols.ctypes.data_as(P32), B)
+    return ehat, status, rounds, nclus, ncols, iters_used, bp_status, pred, llr
+
+
 class SyndromeLossFn(torch.autograd.Function):
     """Batch-summed syndrome loss; backward scales the kernel's d loss / d pred."""
 

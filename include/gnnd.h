@@ -1005,6 +1005,102 @@ int gnnd_belief_find_host(const int64_t* h_var, const int64_t* h_chk, int64_t nu
                           int32_t* h_bp_status, void* h_ehat, int32_t* h_status,
                           int32_t* h_rounds, int32_t* h_nfull, int32_t* h_events, int64_t batch);
 
+/* ---- localized-statistics decoding (BP+LSD): clusters solved locally --------------------------
+ * gnnd_lsd grows clusters around the unsatisfied checks, as union-find does, but on any Tanner
+ * graph, and solves each cluster by gnnd_osd0's elimination restricted to the cluster's own
+ * columns ("LSD-0"): the elimination is as large as the error, not as the code.  Per codeword, T =
+ * float / double; the inputs and conventions are gnnd_osd0's: the target t_c = (x[b*N + V + c] <
+ * 0), and from p = d_pred and `base` the base vector z, the key and the column `order`, computed
+ * exactly as gnnd_osd0 computes them (a NaN: key -inf, z 0; ties to the lower index).  One more
+ * parameter, bits_per_step >= 0.
+ *   s = t xor H^T z;  inV[v] = 0;  inC[c] = s[c];  label[c] = c;  rounds = 0
+ *   if s == 0: ehat = z, status = 0, rounds = nclus = ncols = 0, done
+ *   repeat
+ *     rounds += 1
+ *     active checks   round 1: every c with inC[c]; later: every c with inC[c] whose label is
+ *                     invalid
+ *     candidates      of a cluster K: the variables v with inV[v] == 0 adjacent to an active check
+ *                     labelled K
+ *     join            bits_per_step == 0: every candidate of every active cluster;
+ *                     bits_per_step == k > 0: per active cluster its k candidates that come first
+ *                     in `order` (all of them if it has fewer); the union over the clusters joins
+ *     no variable joined: status = 1, ehat = z, stop            (the failure of gnnd_osd0)
+ *     closure         inV[v] = 1 for the joined v; inC[c] = 1 for every check adjacent to one
+ *     labels          the connected components of the subgraph induced by {v: inV[v]} and
+ *                     {c: inC[c]}; label[c] = the smallest check index of c's component
+ *     eliminate       gnnd_osd0's Gauss-Jordan on freshly built rows with the syndrome word s,
+ *                     walking `order` but skipping every v with inV[v] == 0 (the first unused row
+ *                     holding the column is the pivot)
+ *     invalid labels  label[r] of every unused row r left with s_r = 1
+ *     none: e[pivot column of row r] = s_r for the used rows, ehat = z xor e, status = 0, stop
+ * Every round adds a variable or stops: at most V + 1 rounds.
+ * Outputs: d_ehat [B*V] in dtype, exactly 0.0 / 1.0, required.  d_status, d_rounds, d_nclus (the
+ * number of clusters at the end: the distinct labels over the checks of inC) and d_ncols (the
+ * variables of inV at the end) are int32 [B]; each may be NULL.  Everything is integers once
+ * `order` exists: all outputs are bit-reproducible and equal to the host mirror's in both dtypes.
+ * Guarantees:
+ *   status   d_status equals gnnd_osd0's on every input, for every bits_per_step: a cluster that
+ *            cannot grow is a whole connected component of the graph whose system has no
+ *            solution, and conversely.
+ *   estimate where d_status[b] == 0, d_ehat of b satisfies the syndrome exactly, and is bit for bit
+ *            what gnnd_osd0 returns when its column order is the final cluster variables first,
+ *            in `order` order, then the others in `order` order: after the cluster columns every
+ *            unused row has s = 0, so the later pivots add nothing.
+ * Kernel: one launch on `stream`, one wave per codeword on a wave-private LDS tile, no host sync
+ * (capturable).  The tile is gnnd_osd0's (rows, keys, order, pivots, estimate) and three int32 per
+ * check (the label and two cluster slots); the inverse order and the inV flags reuse the bytes of
+ * the keys.  The rows are rebuilt from the graph every round: no second copy of the matrix.
+ * A NULL g, d_x, d_pred or d_ehat, a base outside the enum, a negative bits_per_step, a dtype
+ * outside the enum: GNND_ERR_INVALID_ARG.  GNND_BF16, C > 2048, or a tile over 64 KiB:
+ * GNND_ERR_UNSUPPORTED.  All decided before any device call, nothing launched.  batch 0 returns
+ * GNND_OK.  gnnd_lsd_host is the host mirror (no device, no tile limit).
+ *
+ * gnnd_lsd_gated is gnnd_lsd on the codewords the caller's gate selects: semantics, pass-through
+ * rule (d_llr < 0 if d_llr is not NULL, else d_pred > 0.5), workspace (gnnd_osd_gated_workspace)
+ * and launch structure (the same device-side compaction, then the LSD kernel over the list, its
+ * length read on the device; two launches, no host sync) are gnnd_osd_gated's.  A pass-through
+ * codeword gets status = rounds = nclus = ncols = 0.  d_gate and d_work are required too; a short
+ * workspace: GNND_ERR_INVALID_ARG; batch > 2^31 - 2: GNND_ERR_UNSUPPORTED.
+ *
+ * gnnd_bplsd is gnnd_minsum(d_x, alpha, beta, iters, early_stop -> d_pred, d_llr, d_iters,
+ * d_bp_status) followed by gnnd_lsd_gated(d_x, d_pred, d_llr, gate = d_bp_status, base,
+ * bits_per_step -> d_ehat, d_status, d_rounds, d_nclus, d_ncols) on the same stream: gnnd_bposd
+ * argument for argument, with bits_per_step for (method, order) and the three counters for
+ * d_choice.  Three launches, no host sync.  d_pred, d_llr, d_bp_status and d_ehat are required.
+ * Where d_bp_status[b] == 0 every output gnnd_bposd shares is gnnd_bposd's, bit for bit; elsewhere
+ * d_ehat is gnnd_lsd's estimate on min-sum's soft output (d_pred as for gnnd_bposd: the mirror's
+ * bits in GNND_F64).  Every GNND_ERR_INVALID_ARG of either stage is decided before the first
+ * device call; GNND_ERR_UNSUPPORTED is the union of both stages' conditions, with nothing
+ * launched; batch 0 returns GNND_OK.  gnnd_lsd_gated_host and gnnd_bplsd_host are the mirrors.  */
+int gnnd_lsd(const gnnd_graph* g, int dtype, const void* d_x, const void* d_pred, int base,
+             int32_t bits_per_step, void* d_ehat, int32_t* d_status, int32_t* d_rounds,
+             int32_t* d_nclus, int32_t* d_ncols, int64_t batch, void* stream);
+int gnnd_lsd_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges, int32_t num_var,
+                  int32_t num_chk, int dtype, const void* h_x, const void* h_pred, int base,
+                  int32_t bits_per_step, void* h_ehat, int32_t* h_status, int32_t* h_rounds,
+                  int32_t* h_nclus, int32_t* h_ncols, int64_t batch);
+int gnnd_lsd_gated(const gnnd_graph* g, int dtype, const void* d_x, const void* d_pred,
+                   const void* d_llr, const int32_t* d_gate, int base, int32_t bits_per_step,
+                   void* d_ehat, int32_t* d_status, int32_t* d_rounds, int32_t* d_nclus,
+                   int32_t* d_ncols, void* d_work, int64_t work_bytes, int64_t batch,
+                   void* stream);
+int gnnd_lsd_gated_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                        int32_t num_var, int32_t num_chk, int dtype, const void* h_x,
+                        const void* h_pred, const void* h_llr, const int32_t* h_gate, int base,
+                        int32_t bits_per_step, void* h_ehat, int32_t* h_status,
+                        int32_t* h_rounds, int32_t* h_nclus, int32_t* h_ncols, int64_t batch);
+int gnnd_bplsd(const gnnd_graph* g, int dtype, const void* d_x, double alpha, double beta,
+               int32_t iters, int32_t early_stop, int base, int32_t bits_per_step, void* d_pred,
+               void* d_llr, int32_t* d_iters, int32_t* d_bp_status, void* d_ehat,
+               int32_t* d_status, int32_t* d_rounds, int32_t* d_nclus, int32_t* d_ncols,
+               void* d_work, int64_t work_bytes, int64_t batch, void* stream);
+int gnnd_bplsd_host(const int64_t* h_var, const int64_t* h_chk, int64_t num_edges,
+                    int32_t num_var, int32_t num_chk, int dtype, const void* h_x, double alpha,
+                    double beta, int32_t iters, int32_t early_stop, int base,
+                    int32_t bits_per_step, void* h_pred, void* h_llr, int32_t* h_iters,
+                    int32_t* h_bp_status, void* h_ehat, int32_t* h_status, int32_t* h_rounds,
+                    int32_t* h_nclus, int32_t* h_ncols, int64_t batch);
+
 /* Adam(torch.optim.Adam update order, amsgrad/maximize off) on one flat parameter buffer of
  * n values with its two moment buffers; *d_step is the device-resident step count (double,
  * incremented by the call), so a whole training step with the update can be captured in one
