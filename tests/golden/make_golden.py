@@ -817,10 +817,67 @@ def gen_v22():
          **sd_to_np(sd), **grads_of(model))
 
 
+SYN_GRAPHS = ('syn_hub', 'syn_leaf', 'syn_g16', 'syn_full8')
+SYN_MODELS = (
+    # (model, script, classes, fp64)
+    ('cgnni', 'classical/CGNNI.py', {'MessagePassing', 'GatedGraphConv', 'GNNI'}, False),
+    ('cbp', 'classical/BP.py', {'MessagePassing', 'GatedGraphConv', 'GNNI'}, False),
+    ('qbp', 'quantum/BP.py', {'MessagePassing', 'GatedGraphConv', 'GNNI'}, True),
+    ('qgnni', 'quantum/QGNNI.py', {'MessagePassing', 'GraphConv', 'GNNI'}, True),
+    ('v24', 'quantum/decoder_v2_4.py', {'scatter_mean', 'scatter_', 'MessagePassing', 'GraphConv',
+                                        'GNNI', 'init_weights', 'init_weights_2'}, True),
+    ('nbp', 'quantum/neural_BP.py', {'MessagePassing', 'GraphConv', 'GNNI'}, True),
+    ('v10', 'quantum/decoder_v1_0.py', {'MessagePassing', 'GraphConv', 'GNNI'}, True),
+    ('v30', 'quantum/decoder_v3_0.py', {'MessagePassing', 'GraphConv', 'GNNI'}, True),
+)
+
+
+def gen_synthetic():
+    """The irregular graphs of tests/synthetic_codes.py (a hub graph with variables of degree 38,
+    one with checks of degree 1 and 0 and an isolated variable, one with a check of degree 40, one
+    with every check of degree 8) through the reference's own classes, H swapped in as gen_ldpc
+    does: B = 2, T = 3, seeded default init (neural_BP / decoder_v1_0: the scripts' all-ones init
+    perturbed as in gen_neural_bp), inputs from synthetic_codes.decode_inputs.  Every reference
+    class takes its graph from the globals rows, cols, H alone, so all eight accept a non-toric H;
+    decoder_v2_2 is left out: its weights are shared by the eight edge types of the toric code
+    (feat_onehot), which no other graph has.  Writes syn_<graph>_<model>.npz with H, x_B2, w/*
+    and out_B2_T3 (decoder_v3_0: out0_B2_T3 and out1_B2_T3)."""
+    tests = os.path.dirname(OUT)
+    if tests not in sys.path:
+        sys.path.insert(0, tests)
+    import synthetic_codes as sc
+    B, T = 2, 3
+    for gi, graph in enumerate(SYN_GRAPHS):
+        Hn = sc.decode_matrix(graph)
+        for mi, (model, script, names, f64) in enumerate(SYN_MODELS):
+            H = torch.from_numpy(Hn.astype(np.float64 if f64 else np.float32))
+            V, C = H.shape
+            ns = load_ref(script, names)
+            ns['rows'], ns['cols'], ns['BATCH_SIZE'], ns['H'], ns['Nc'] = V, C, B, H, T
+            set_seed(900 + 10 * gi + mi)
+            m0 = ns['GNNI'](T)
+            if model in ('nbp', 'v10'):
+                with torch.no_grad():
+                    for k, p in m0.named_parameters():
+                        if k == 'alpha':
+                            p.fill_(0.3)
+                        else:
+                            p.mul_(1 + 0.25 * torch.randn(p.shape, dtype=p.dtype))
+            sd = {k: v.clone() for k, v in m0.state_dict().items()}
+            x = torch.from_numpy(sc.decode_inputs(graph, model, B, seed=7))
+            out, _ = run_model(ns, H, x, B, T, sd)
+            arrays = dict(sd_to_np(sd), H=Hn, x_B2=x.numpy())
+            if model == 'v30':
+                arrays['out0_B2_T3'], arrays['out1_B2_T3'] = out[0].numpy(), out[1].numpy()
+            else:
+                arrays['out_B2_T3'] = out.numpy()
+            save(f'{graph}_{model}', **arrays)
+
+
 if __name__ == '__main__':
     torch.set_num_threads(1)
     which = sys.argv[1:] or ['classical', 'quantum', 'training', 'neural_bp', 'ldpc', 'fer', 'v30',
-                             'v22']
+                             'v22', 'synthetic']
     if 'classical' in which:
         gen_classical()
     if 'quantum' in which:
@@ -837,3 +894,5 @@ if __name__ == '__main__':
         gen_v30()
     if 'v22' in which:
         gen_v22()
+    if 'synthetic' in which:
+        gen_synthetic()

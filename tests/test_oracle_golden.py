@@ -21,6 +21,11 @@ DECODERS = [
     ('cgnni_ldpc_randinit', 'cgnni', 'ldpc_648_324_graph'),
     ('bp_ldpc', 'cbp', 'ldpc_648_324_graph'),
 ]
+# the irregular graphs of tests/synthetic_codes.py (make_golden.py gen_synthetic): the fixture holds
+# its own H
+SYN_GRAPHS = ('syn_hub', 'syn_leaf', 'syn_g16', 'syn_full8')
+SYN_MODELS = ('cgnni', 'cbp', 'qbp', 'qgnni', 'v24', 'nbp', 'v10')
+DECODERS += [(f'{g}_{m}', m, f'{g}_{m}') for g in SYN_GRAPHS for m in SYN_MODELS]
 
 
 def _cases():
@@ -44,6 +49,28 @@ def test_oracle_decoder_matches_reference(golden, fx, model, gfx, B, T):
     else:
         np.testing.assert_allclose(out, ref, rtol=1e-10, atol=1e-13)
     assert ((out > 0.5) == (ref > 0.5)).all()
+
+
+@pytest.mark.parametrize('graph', SYN_GRAPHS)
+def test_oracle_v30_matches_reference_on_synthetic_graph(golden, graph):
+    """decoder_v3_0's two readout tensors, at the tolerances above."""
+    import synthetic_codes as sc
+    z = golden(f'{graph}_v30')
+    assert np.array_equal(z['H'], sc.decode_matrix(graph))
+    out = O.decode('v30', z['H'], z['x_B2'], 3, weights_of(z))
+    for o, ref in zip(out, (z['out0_B2_T3'], z['out1_B2_T3'])):
+        assert o.shape == ref.shape and o.dtype == ref.dtype == np.float64
+        np.testing.assert_allclose(o, ref, rtol=1e-10, atol=1e-13)
+        assert ((o > 0.5) == (ref > 0.5)).all()
+
+
+@pytest.mark.parametrize('graph', SYN_GRAPHS)
+@pytest.mark.parametrize('model', SYN_MODELS)
+def test_synthetic_fixture_holds_the_graph_and_inputs(golden, graph, model):
+    import synthetic_codes as sc
+    z = golden(f'{graph}_{model}')
+    assert np.array_equal(z['H'], sc.decode_matrix(graph))
+    assert np.array_equal(z['x_B2'], sc.decode_inputs(graph, model, 2, seed=7))
 
 
 def _prop_cases():
