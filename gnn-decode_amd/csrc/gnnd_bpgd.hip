@@ -8,8 +8,6 @@
 #include "gnnd_wave_tile.h"
 #include "gnnd_bpgd_host.h"
 
-// this translation unit's debug word: gnnd_debug_take_bpgd() (tests/bpgd_debug_worker.py reads it
-// next to gnnd_debug_flags)
 GNND_DEBUG_TU(bpgd)
 
 // ---------------------------------------------------------------------------------------

@@ -46,7 +46,15 @@ __device__ __forceinline__ int gnnd_dcheck_idx(int i, int n, int bit) {
 #define GNND_DIDX(i, n, bit) gnnd_dcheck_idx((i), (n), (bit))
 #define GNND_DCHECK(cond, bit) \
     do { if (!(cond)) atomicOr(&g_gnnd_debug_word, 1u << (bit)); } while (0)
-// per-TU host getter: returns and clears this translation unit's debug word
+// per-TU host getter: returns and clears this translation unit's debug word.  The rule: every
+// translation unit states GNND_DEBUG_TU(name) once, and that line is all it takes to be collected:
+// the macro also links the getter into the list gnnd_debug_flags walks (gnnd_decode.hip), from a
+// static initialiser that makes no HIP call.  tests/test_abi.py holds every Makefile SRC unit to it.
+struct GnndDebugTu {
+    unsigned (*take)(void);
+    GnndDebugTu* next;
+    explicit GnndDebugTu(unsigned (*t)(void));   // gnnd_decode.hip: pushes this onto the list
+};
 #define GNND_DEBUG_TU(name)                                                            \
     extern "C" unsigned gnnd_debug_take_##name(void) {                                \
         unsigned v = 0;                                                                \
@@ -54,7 +62,8 @@ __device__ __forceinline__ int gnnd_dcheck_idx(int i, int n, int bit) {
         const unsigned z = 0;                                                          \
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_gnnd_debug_word), &z, sizeof(z));         \
         return v;                                                                      \
-    }
+    }                                                                                  \
+    static GnndDebugTu g_gnnd_debug_tu(gnnd_debug_take_##name);
 #else
 #define GNND_DIDX(i, n, bit) (i)
 #define GNND_DCHECK(cond, bit) do { } while (0)

@@ -199,11 +199,10 @@ extern "C" int gnnd_decode(const gnnd_graph* g, int model, int dtype, const void
 // ---------------------------------------------------------------------------------------
 // debug build: collect every translation unit's check word (gnnd_common.h GNND_DEBUG_TU)
 // ---------------------------------------------------------------------------------------
-#define GNND_TU_LIST(X) X(graph) X(propagate) X(decode) X(decode_v24) X(decode_qgnni) \
-    X(decode_qbp) X(decode_cgnni) X(decode_cbp) X(decode_nbp) X(decode_v10) X(decode_v30) \
-    X(decode_v22) X(train) X(sample) X(osd)
-#define GNND_DECL_TU(n) extern "C" unsigned gnnd_debug_take_##n(void);
-GNND_TU_LIST(GNND_DECL_TU)
+#ifdef GNND_DEBUG
+static GnndDebugTu* g_debug_tus;   // zero-initialised: valid before any unit's static initialiser
+GnndDebugTu::GnndDebugTu(unsigned (*t)(void)) : take(t), next(g_debug_tus) { g_debug_tus = this; }
+#endif
 
 extern "C" int gnnd_debug_enabled(void) {
 #ifdef GNND_DEBUG
@@ -219,8 +218,9 @@ extern "C" int gnnd_debug_flags(uint32_t* h_flags) {
     if (!h_flags) return GNND_ERR_INVALID_ARG;
     GNND_HIP_CHECK(hipDeviceSynchronize());
     unsigned v = 0;
-#define GNND_TAKE_TU(n) v |= gnnd_debug_take_##n();
-    GNND_TU_LIST(GNND_TAKE_TU)
+#ifdef GNND_DEBUG
+    for (GnndDebugTu* tu = g_debug_tus; tu; tu = tu->next) v |= tu->take();
+#endif
     *h_flags = v;
     return GNND_OK;
 }

@@ -8,8 +8,6 @@
 #include "gnnd_lsd_host.h"
 #include "gnnd_osd_tile.h"
 
-// this translation unit's debug word: gnnd_debug_take_lsd() (tests/lsd_debug_worker.py reads it
-// next to gnnd_debug_flags)
 GNND_DEBUG_TU(lsd)
 
 // ---------------------------------------------------------------------------------------

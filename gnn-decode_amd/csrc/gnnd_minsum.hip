@@ -10,9 +10,6 @@
 #include "gnnd_ufw_host.h"
 #include "gnnd_lsd_host.h"
 
-// this translation unit's debug word: gnnd_debug_take_minsum() (the collector list of
-// gnnd_debug_flags lives in the decoder's translation unit, which this feature leaves alone;
-// tests/minsum_debug_worker.py reads both)
 GNND_DEBUG_TU(minsum)
 
 // ---------------------------------------------------------------------------------------

@@ -8,8 +8,6 @@
 #include "gnnd_wave_tile.h"
 #include "gnnd_minsum_layered_host.h"
 
-// this translation unit's debug word: gnnd_debug_take_minsum_layered() (the pattern of
-// gnnd_minsum.hip; tests/minsum_layered_debug_worker.py reads it)
 GNND_DEBUG_TU(minsum_layered)
 
 // ---------------------------------------------------------------------------------------

@@ -10,8 +10,6 @@
 #include "gnnd_wave_tile.h"
 #include "gnnd_relay_host.h"
 
-// this translation unit's debug word: gnnd_debug_take_relay() (tests/relay_debug_worker.py reads it
-// next to gnnd_debug_flags)
 GNND_DEBUG_TU(relay)
 
 // ---------------------------------------------------------------------------------------

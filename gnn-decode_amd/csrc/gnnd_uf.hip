@@ -6,8 +6,6 @@
 #include "gnnd_uf_host.h"
 #include "gnnd_uf_tile.h"
 
-// this translation unit's debug word: gnnd_debug_take_uf() (tests/uf_debug_worker.py reads it next
-// to gnnd_debug_flags)
 GNND_DEBUG_TU(uf)
 
 // ---------------------------------------------------------------------------------------

@@ -7,8 +7,6 @@
 #include "gnnd_ufw_host.h"
 #include "gnnd_uf_tile.h"
 
-// this translation unit's debug word: gnnd_debug_take_ufw() (tests/ufw_debug_worker.py reads it
-// next to gnnd_debug_flags)
 GNND_DEBUG_TU(ufw)
 
 // ---------------------------------------------------------------------------------------

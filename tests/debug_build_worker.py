@@ -2,17 +2,10 @@
 libgnnd_debug.so or the release library): decodes every model on its configs' codes,
 propagates on both kernels, samples inputs and runs one fused training step, then prints
 one JSON line with the debug flags and a checksum of every output."""
-import json
-import os
-import sys
-
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, 'gnn-decode_amd'))
+from debug_child import report  # first: it puts the package on sys.path
 import gnndecode as gd  # noqa: E402
-from gnndecode import _lib  # noqa: E402
 
 
 def main():
@@ -56,15 +49,7 @@ def main():
     tr2 = gd.train.FusedV24Trainer(m, lf, graph=False)
     sums['train'] = float(tr2.step(gd.data.make_batch(x, m.graph(dev)), y))
     del tr
-    flags = ctypes_flags()
-    print(json.dumps({'debug': _lib.get().gnnd_debug_enabled(), 'flags': flags, 'sums': sums}))
-
-
-def ctypes_flags():
-    import ctypes
-    f = ctypes.c_uint32()
-    _lib.call('gnnd_debug_flags', ctypes.byref(f))
-    return int(f.value)
+    report(sums=sums)
 
 
 if __name__ == '__main__':

@@ -5,9 +5,7 @@ libgnnd_debug.so, test_debug_library_runs_every_case_clean) it queries the plan 
 case of synthetic_codes.DECODE_PLAN_CASES at its smallest batch for T in DECODE_ITERS, saves the
 outputs to the .npz file named on the command line for the parent to compare bit for bit with the
 release run, and prints one JSON line with the plans and gnnd_debug_flags (which synchronises the
-device and collects every decoder translation unit's bounds-check word)."""
-import ctypes
-import json
+device and collects every translation unit's bounds-check word)."""
 import os
 import sys
 import zlib
@@ -15,12 +13,9 @@ import zlib
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(ROOT, 'gnn-decode_amd'), os.path.join(ROOT, 'tests')):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+from debug_child import ROOT, report  # first: it puts the package on sys.path
 import gnndecode as gd  # noqa: E402
-from gnndecode import _lib, ops  # noqa: E402
+from gnndecode import ops  # noqa: E402
 import synthetic_codes as sc  # noqa: E402
 
 DEV = 'cuda:0'
@@ -98,11 +93,8 @@ def main():
         plans['-'.join(case[:3])] = [p['kernel'], p['items_per_lane'], p['var_group']]
         for T in sc.DECODE_ITERS:
             arrays[key(case, T)] = run_case(case, T)
-    f = ctypes.c_uint32()
-    _lib.call('gnnd_debug_flags', ctypes.byref(f))
     np.savez(sys.argv[1], **arrays)
-    print(json.dumps({'debug': _lib.get().gnnd_debug_enabled(), 'flags': int(f.value),
-                      'cases': len(sc.DECODE_PLAN_CASES), 'plans': plans}))
+    report(cases=len(sc.DECODE_PLAN_CASES), plans=plans)
 
 
 if __name__ == '__main__':

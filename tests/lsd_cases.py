@@ -1,4 +1,4 @@
-"""Shared by tests/test_lsd_cpu.py, tests/test_gpu_lsd.py and tests/lsd_debug_worker.py: an
+"""Shared by tests/test_lsd_cpu.py, tests/test_gpu_lsd.py and tests/decoder_debug_worker.py: an
 independent numpy statement of localized-statistics decoding (include/gnnd.h, gnnd_lsd), written
 from the definition with sets and dense matrices, and the seeded inputs of tests/osd_cases.py
 and tests/minsum_cases.py on the shipped codes and the synthetic graphs.  The statement also

@@ -4,22 +4,16 @@ on the tall graph) through the ops, outputs as numpy arrays.  The tests call run
 the release library.  As a program (a child process with GNND_LIB pointing at libgnnd_debug.so,
 test_debug_library_runs_every_case_clean) it runs every case, saves the outputs to the .npz file
 named on the command line for the parent to compare with the references, and prints one JSON line
-with the debug flags: gnnd_debug_flags synchronises the device and collects the OSD and decoder
-translation units' words, the min-sum, layered and relay units' words are taken one by one."""
-import ctypes
-import json
-import os
+with the debug flags (gnnd_debug_flags synchronises the device and collects every translation
+unit's word)."""
 import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(ROOT, 'gnn-decode_amd'), os.path.join(ROOT, 'tests')):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+from debug_child import report  # first: it puts the package on sys.path
 import gnndecode as gd  # noqa: E402
-from gnndecode import _lib, ops  # noqa: E402
+from gnndecode import ops  # noqa: E402
 import bposd_cases as bc  # noqa: E402
 import minsum_cases as mc  # noqa: E402
 import osd_cases as oc  # noqa: E402
@@ -29,7 +23,6 @@ import synthetic_codes as sc  # noqa: E402
 DEV = 'cuda:0'
 DTYPES = ('float32', 'float64')
 BASES = ('zero', 'hard')
-TAKE = ('gnnd_debug_take_minsum', 'gnnd_debug_take_minsum_layered', 'gnnd_debug_take_relay')
 
 CASES = ([('minsum', code, B, dt, sch) for code, B in sc.MINSUM_SHAPES for dt in DTYPES
           for sch in ('flooding', 'layered')]
@@ -121,17 +114,8 @@ def main():
     for case in CASES:
         for j, a in enumerate(run(case)):
             arrays[key(case, j)] = a
-    f = ctypes.c_uint32()
-    _lib.call('gnnd_debug_flags', ctypes.byref(f))
-    flags = int(f.value)
-    for name in TAKE:
-        take = getattr(_lib.get(), name)
-        take.restype = ctypes.c_uint
-        take.argtypes = []
-        flags |= int(take())
     np.savez(sys.argv[1], **arrays)
-    print(json.dumps({'debug': _lib.get().gnnd_debug_enabled(), 'flags': flags,
-                      'cases': len(CASES)}))
+    report(cases=len(CASES))
 
 
 if __name__ == '__main__':

@@ -52,6 +52,20 @@ def test_every_header_symbol_is_exported_and_bound():
     assert sorted(_lib.SIGNATURES) == names, 'ctypes signature table out of sync with gnnd.h'
 
 
+def test_every_translation_unit_registers_its_debug_word():
+    """gnnd_debug_flags collects the units that state GNND_DEBUG_TU (gnnd_common.h: the macro links
+    the unit's getter into the collector's list), so every unit the Makefile builds states it
+    exactly once, and no hand-kept list of units is left to fall behind SRC."""
+    pkg = os.path.join(ROOT, 'gnn-decode_amd')
+    src = re.search(r'^SRC\s*:=\s*(.*)$', open(os.path.join(pkg, 'Makefile')).read(), re.M)
+    units = src.group(1).split()
+    assert len(units) >= 24 and all(u.endswith('.hip') for u in units), units
+    for u in units:
+        code = re.sub(r'//[^\n]*', '', open(os.path.join(pkg, u)).read())
+        assert len(re.findall(r'\bGNND_DEBUG_TU\(', code)) == 1, u
+    assert 'GNND_TU_LIST' not in open(os.path.join(pkg, 'csrc', 'gnnd_decode.hip')).read()
+
+
 def test_status_strings():
     for s in range(6):
         assert _lib.status_string(s)

@@ -9,10 +9,6 @@ the raw ABI, a non-finite codeword, stream capture, the registered ops, the boun
 library, and the hand-over to ops.osd_gated."""
 import ctypes
 import gc
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -22,14 +18,12 @@ import gnndecode as gd
 from gnndecode import _lib, ops
 
 import bpgd_cases as bc
+import debug_child
 import minsum_cases as mc
 
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, 'gnn-decode_amd', 'gnndecode')
-DEBUG_LIB = os.path.join(PKG, 'libgnnd_debug.so')
 
 # toric-5 (V = 100: lanes 36 .. 63 own one variable, the others two) at B = 9 (three workgroups, the
 # last with one wave) and B = 67 (the last partial workgroup); toric-7 (V = 196: three or four
@@ -330,14 +324,7 @@ def test_debug_library_runs_bpgd_clean():
     """toric-5 B = 67 (fp64, both picks) and syn_hub B = 9 (fp32, every variable decimated) under
     the bounds-checked build (GNND_LIB, a fresh child process): no index check fires and the bits
     are the numpy reference's."""
-    assert os.path.exists(DEBUG_LIB), 'build it: make -C gnn-decode_amd debug'
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'bpgd_debug_worker.py')],
-                       env=dict(os.environ, GNND_LIB=DEBUG_LIB), capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])
-    assert res['debug'] == 1
-    assert res['flags'] == 0, f"debug index checks fired: bits {res['flags']:#x}"
+    res = debug_child.run('decoder_debug_worker.py', 'bpgd')
     assert res['equal'] and all(res['equal'].values()), res['equal']
 
 

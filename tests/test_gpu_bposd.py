@@ -6,10 +6,6 @@ batch beyond the grid cap), every output element written for every gate, the tin
 sample_toric -> bposd -> decision_errors, stream capture with the gated count changing between
 replays, the registered ops and the bounds-checked debug library."""
 import ctypes
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,15 +15,13 @@ import gnndecode as gd
 from gnndecode import _lib, ops
 
 import bposd_cases as bc
+import debug_child
 import minsum_cases as mc
 import osd_cases as oc
 
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, 'gnn-decode_amd', 'gnndecode')
-DEBUG_LIB = os.path.join(PKG, 'libgnnd_debug.so')
 
 # toric-5 B = 1 (count 0, then count 1), 5 (a partial workgroup) and 67 (16 workgroups and a tail
 # at count B, fewer list entries than waves in flight under the mixed gates); toric-7: C = 96, two
@@ -422,12 +416,5 @@ def test_traces_as_registered_ops():
 def test_debug_library_runs_bposd_clean():
     """toric-5 B = 67 and the rank-deficient graph under the bounds-checked build (GNND_LIB, a
     fresh child process): no index check fires and the bits are the host mirror's."""
-    assert os.path.exists(DEBUG_LIB), 'build it: make -C gnn-decode_amd debug'
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'bposd_debug_worker.py')],
-                       env=dict(os.environ, GNND_LIB=DEBUG_LIB), capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])
-    assert res['debug'] == 1
-    assert res['flags'] == 0, f"debug index checks fired: bits {res['flags']:#x}"
+    res = debug_child.run('decoder_debug_worker.py', 'bposd')
     assert res['equal'] == {'toric_5_bposd': True, 'toric_5_gated': True, 'bch_dup_gated': True}

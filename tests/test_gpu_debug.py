@@ -2,24 +2,20 @@
 every model / kernel family runs under it without a single index-check violation, and its
 outputs equal the release library's (the checks never change values; the generic
 propagate kernels accumulate with float atomics, so those sums agree to 1e-12)."""
-import json
 import os
-import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, 'gnn-decode_amd', 'gnndecode')
-DEBUG_LIB = os.path.join(PKG, 'libgnnd_debug.so')
+import debug_child
+from debug_child import DEBUG_LIB, PKG
 
 
 def _run(lib):
-    env = dict(os.environ, GNND_LIB=lib)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'debug_build_worker.py')],
-                       env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return json.loads(r.stdout.strip().splitlines()[-1])
+    """debug_build_worker.py on `lib`; on the debug library through the harness, which asserts
+    that it is the debug build and that no index check fired."""
+    if lib == DEBUG_LIB:
+        return debug_child.run('debug_build_worker.py', timeout=600)
+    return debug_child.spawn(lib, 'debug_build_worker.py', timeout=600)
 
 
 def test_debug_library_exports_and_reports_enabled():

@@ -16,11 +16,6 @@ below).  decoder_v2_2 is not run: gd.MODELS['v22'] raises on a non-toric H witho
 
 Tolerances are those of tests/test_gpu_parity.py.  No case needed the fp32 conditioning criterion
 (CONDITIONED is empty)."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
@@ -28,13 +23,12 @@ import torch
 import gnn_oracle as O
 from gnndecode import _lib, ops
 
+import debug_child
 import decode_synthetic_debug_worker as work
 import synthetic_codes as sc
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEBUG_LIB = os.path.join(ROOT, 'gnn-decode_amd', 'gnndecode', 'libgnnd_debug.so')
 KERNEL = {'R': 'decode_resident_kernel', 'S': 'decode_kernel'}
 # fp32 cases judged by the criterion of test_classical_bp_fp32_conditioning_at_scale instead of the
 # fixed tolerance: (graph, model, dtype) -> the measured ratio of the GPU's error against the fp64
@@ -103,16 +97,9 @@ def assert_parity(case, got, x, T, w, tag):
 # would read through it
 # ------------------------------------------------------------------------------------------------
 def test_debug_library_runs_every_case_clean(tmp_path):
-    assert os.path.exists(DEBUG_LIB), 'build it: make -C gnn-decode_amd debug'
     npz = str(tmp_path / 'outputs.npz')
-    r = subprocess.run([sys.executable,
-                        os.path.join(ROOT, 'tests', 'decode_synthetic_debug_worker.py'), npz],
-                       env=dict(os.environ, GNND_LIB=DEBUG_LIB), capture_output=True, text=True,
-                       timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])
-    assert res['debug'] == 1 and res['cases'] == len(sc.DECODE_PLAN_CASES)
-    assert res['flags'] == 0, f"debug index checks fired: bits {res['flags']:#x}"
+    res = debug_child.run('decode_synthetic_debug_worker.py', npz, timeout=600)
+    assert res['cases'] == len(sc.DECODE_PLAN_CASES)
     for case in sc.DECODE_PLAN_CASES:
         assert res['plans'][_id(case)] == [KERNEL[case[3]], case[4], case[5]], _id(case)
     with np.load(npz) as z:

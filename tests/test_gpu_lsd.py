@@ -6,10 +6,6 @@ in pred; bplsd on toric-5 against its mirror and against bposd on the pass-throu
 capture; the registered ops; the LDS boundary on rings; the bounds-checked debug library."""
 import ctypes
 import gc
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,14 +15,13 @@ import gnndecode as gd
 from gnndecode import _lib, ops
 
 import bposd_cases as bc
+import debug_child
 import lsd_cases as lc
 import osd_cases as oc
 
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEBUG_LIB = os.path.join(ROOT, 'gnn-decode_amd', 'gnndecode', 'libgnnd_debug.so')
 
 _GRAPHS = {}
 
@@ -349,12 +344,5 @@ def test_debug_library_runs_lsd_clean():
     """toric-5 (fp64), syn_c65 (fp32) and syn_tall (fp64, with unsolvable codewords) through ops.lsd
     with bits_per_step 0 and 1, and bplsd on toric-5, under the bounds-checked build (GNND_LIB, a
     fresh child process): no index check fires and the bits are the statement's."""
-    assert os.path.exists(DEBUG_LIB), 'build it: make -C gnn-decode_amd debug'
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'lsd_debug_worker.py')],
-                       env=dict(os.environ, GNND_LIB=DEBUG_LIB), capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])
-    assert res['debug'] == 1
-    assert res['flags'] == 0, f"debug index checks fired: bits {res['flags']:#x}"
+    res = debug_child.run('decoder_debug_worker.py', 'lsd')
     assert res['equal'] and all(res['equal'].values()), res['equal']

@@ -6,10 +6,6 @@ check degree 24, fewer waves per workgroup), the early exit returning exactly th
 iteration, minsum -> osd -> decision_errors end to end, stream capture, the registered ops and the
 bounds-checked debug library."""
 import ctypes
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,14 +14,12 @@ import torch
 import gnndecode as gd
 from gnndecode import _lib, ops
 
+import debug_child
 import minsum_cases as mc
 
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, 'gnn-decode_amd', 'gnndecode')
-DEBUG_LIB = os.path.join(PKG, 'libgnnd_debug.so')
 
 # toric-5: V = 100 (not a multiple of 64), B = 1 / 5 / 67: one wave, a partial workgroup, 16 full
 # workgroups + a 3-wave tail, every parameter set; toric-7: C = 96, two checks per lane; BCH:
@@ -287,12 +281,5 @@ def test_minsum_traces_as_registered_ops():
 def test_debug_library_runs_minsum_clean():
     """toric-5 B = 67 and LDPC B = 3 under the bounds-checked build (GNND_LIB, a fresh child
     process): no index check fires and the bits are the numpy reference's."""
-    assert os.path.exists(DEBUG_LIB), 'build it: make -C gnn-decode_amd debug'
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'minsum_debug_worker.py')],
-                       env=dict(os.environ, GNND_LIB=DEBUG_LIB), capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])
-    assert res['debug'] == 1
-    assert res['flags'] == 0, f"debug index checks fired: bits {res['flags']:#x}"
+    res = debug_child.run('decoder_debug_worker.py', 'minsum')
     assert res['equal'] == {'toric_5': True, 'ldpc_648_324': True}

@@ -8,10 +8,6 @@ codeword next to its wave-mates, the early exit returning exactly the state of i
 bposd on the layered schedule, minsum -> osd -> decision_errors, stream capture, the registered
 ops and the bounds-checked debug library."""
 import ctypes
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -20,6 +16,7 @@ import torch
 import gnndecode as gd
 from gnndecode import _lib, ops
 
+import debug_child
 import minsum_cases as mc
 import minsum_layered_cases as lc
 import osd_cases as oc
@@ -27,9 +24,6 @@ import osd_cases as oc
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, 'gnn-decode_amd', 'gnndecode')
-DEBUG_LIB = os.path.join(PKG, 'libgnnd_debug.so')
 
 CASES = ([('toric_5', B, dt, p) for B in (1, 5, 67) for dt in ('float32', 'float64')
           for p in lc.PARAMS]
@@ -415,13 +409,5 @@ def test_traces_as_registered_ops():
 def test_debug_library_runs_layered_clean():
     """toric-5 B = 67 (fp64) and LDPC B = 5 (fp32) under the bounds-checked build (GNND_LIB, a
     fresh child process): no index check fires and the bits are the numpy reference's."""
-    assert os.path.exists(DEBUG_LIB), 'build it: make -C gnn-decode_amd debug'
-    r = subprocess.run([sys.executable,
-                        os.path.join(ROOT, 'tests', 'minsum_layered_debug_worker.py')],
-                       env=dict(os.environ, GNND_LIB=DEBUG_LIB), capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])
-    assert res['debug'] == 1
-    assert res['flags'] == 0, f"debug index checks fired: bits {res['flags']:#x}"
+    res = debug_child.run('decoder_debug_worker.py', 'minsum_layered')
     assert res['equal'] == {'toric_5': True, 'ldpc_648_324': True}

@@ -3,11 +3,6 @@ definition (tests/osd_cases.py), exact equality: the shapes where the one-wave-p
 can go wrong (V not a multiple of 32, grid-stride tail and partial workgroups, more than one row
 per lane, one wave per workgroup, a rank-deficient graph), decode -> osd0 -> decision_errors end
 to end, stream capture, and the bounds-checked debug library."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
@@ -15,14 +10,12 @@ import torch
 import gnndecode as gd
 from gnndecode import ops
 
+import debug_child
 import osd_cases as oc
 
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, 'gnn-decode_amd', 'gnndecode')
-DEBUG_LIB = os.path.join(PKG, 'libgnnd_debug.so')
 
 # toric-5: V = 100 (not a multiple of 32), B = 1 / 5 / 67: one wave, a partial workgroup, 16 full
 # workgroups + a 3-wave tail; toric-7: C = 96, two rows per lane; BCH: V = 63 (one column word and
@@ -160,12 +153,5 @@ def test_osd0_traces_as_registered_op():
 def test_debug_library_runs_osd0_clean():
     """One toric-5 case under the bounds-checked build (GNND_LIB, a fresh child process): no
     index check fires and the bits are the reference's."""
-    assert os.path.exists(DEBUG_LIB), 'build it: make -C gnn-decode_amd debug'
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'osd_debug_worker.py')],
-                       env=dict(os.environ, GNND_LIB=DEBUG_LIB), capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])
-    assert res['debug'] == 1
-    assert res['flags'] == 0, f"debug index checks fired: bits {res['flags']:#x}"
+    res = debug_child.run('decoder_debug_worker.py', 'osd')
     assert res['equal'] == {'zero': True, 'hard': True}

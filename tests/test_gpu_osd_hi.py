@@ -4,11 +4,6 @@ and chosen candidate index: the shapes of tests/test_gpu_osd.py (V not a multipl
 workgroups and the grid-stride tail, one row per lane with the ballot count and several with the
 cross-lane sum, one wave per workgroup, a rank-deficient graph), decode -> osd -> decision_errors
 end to end, stream capture, the registered op, and the bounds-checked debug library."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
@@ -16,14 +11,12 @@ import torch
 import gnndecode as gd
 from gnndecode import _lib, ops
 
+import debug_child
 import osd_hi_cases as hc
 
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, 'gnn-decode_amd', 'gnndecode')
-DEBUG_LIB = os.path.join(PKG, 'libgnnd_debug.so')
 
 # toric-5 in both bases and dtypes; elsewhere one dtype per base.  toric-7: two rows per lane (the
 # cross-lane sum), F = 100 so (cs, 64) is unclamped: 2016 pairs; BCH: C <= 64, the ballot count;
@@ -224,13 +217,6 @@ def test_osd_traces_as_registered_op():
 def test_debug_library_runs_osd_clean():
     """(cs, 10) and (e, 8) on toric-7 and the rank-deficient graph under the bounds-checked build
     (GNND_LIB, a fresh child process): no index check fires and the bits are the reference's."""
-    assert os.path.exists(DEBUG_LIB), 'build it: make -C gnn-decode_amd debug'
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'osd_hi_debug_worker.py')],
-                       env=dict(os.environ, GNND_LIB=DEBUG_LIB), capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])
-    assert res['debug'] == 1
-    assert res['flags'] == 0, f"debug index checks fired: bits {res['flags']:#x}"
+    res = debug_child.run('decoder_debug_worker.py', 'osd_hi')
     assert res['equal'] == {'toric_7_cs': True, 'toric_7_e': True, 'bch_dup_cs': True,
                             'bch_dup_e': True}

@@ -6,10 +6,6 @@ waves per workgroup), solutions replaced by lighter ones and ties, the one-leg z
 against ops.minsum, out= forms, refusals, non-finite inputs, stream capture, the registered ops,
 the bounds-checked debug library, and sample_toric -> relay -> decision_errors end to end."""
 import ctypes
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,15 +14,13 @@ import torch
 import gnndecode as gd
 from gnndecode import _lib, ops
 
+import debug_child
 import minsum_cases as mc
 import relay_cases as rc
 
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, 'gnn-decode_amd', 'gnndecode')
-DEBUG_LIB = os.path.join(PKG, 'libgnnd_debug.so')
 
 # toric-5: V = 100 (not a multiple of 64), B = 1 / 5 / 67: one wave, a partial workgroup, 16 full
 # workgroups + a 3-wave tail, every parameter set; toric-7: two checks per lane; BCH: C = 18 < 64,
@@ -259,14 +253,7 @@ def test_relay_traces_as_registered_ops():
 def test_debug_library_runs_relay_clean():
     """toric-5 B = 67 and LDPC B = 3 under the bounds-checked build (GNND_LIB, a fresh child
     process): no index check fires and the bits are the numpy reference's."""
-    assert os.path.exists(DEBUG_LIB), 'build it: make -C gnn-decode_amd debug'
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'relay_debug_worker.py')],
-                       env=dict(os.environ, GNND_LIB=DEBUG_LIB), capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])
-    assert res['debug'] == 1
-    assert res['flags'] == 0, f"debug index checks fired: bits {res['flags']:#x}"
+    res = debug_child.run('decoder_debug_worker.py', 'relay')
     assert res['equal'] == {'toric_5': True, 'ldpc_648_324': True}
 
 

@@ -7,10 +7,6 @@ composition from the public ops, the guarantees, the one-leg zero-gamma case aga
 LDS boundary of the MEAN tile, out= / work= forms, refusals, a non-finite codeword, stream capture
 with the gate changing between replays, the registered ops and the bounds-checked debug library."""
 import ctypes
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,6 +15,7 @@ import torch
 import gnndecode as gd
 from gnndecode import _lib, ops
 
+import debug_child
 import minsum_cases as mc
 import relay_cases as rc
 import relay_osd_cases as roc
@@ -26,8 +23,6 @@ import relay_osd_cases as roc
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEBUG_LIB = os.path.join(ROOT, 'gnn-decode_amd', 'gnndecode', 'libgnnd_debug.so')
 
 CASES = [(code, B, dt, p) for _, code, B in roc.SHAPES for dt in ('float32', 'float64')
          for p in rc.PARAMS]
@@ -370,14 +365,7 @@ def test_ops_trace_as_registered_ops():
 
 def test_debug_library_runs_relay_osd_clean():
     """toric-5 B = 9 (fp64) and LDPC B = 3 (fp32) in both modes under the bounds-checked build
-    (GNND_LIB, a fresh child process): no index check fires, gnnd_debug_take_relay included, and
-    soft is the numpy statement's."""
-    assert os.path.exists(DEBUG_LIB), 'build it: make -C gnn-decode_amd debug'
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'relay_osd_debug_worker.py')],
-                       env=dict(os.environ, GNND_LIB=DEBUG_LIB), capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])
-    assert res['debug'] == 1
-    assert res['flags'] == 0, f"debug index checks fired: bits {res['flags']:#x}"
+    (GNND_LIB, a fresh child process): no index check fires in any translation unit, and soft is
+    the numpy statement's."""
+    res = debug_child.run('decoder_debug_worker.py', 'relay_osd')
     assert res['equal'] == {'toric_5': True, 'ldpc_648_324': True}

@@ -7,11 +7,6 @@ the last column with unused rows left and no free column, V = 64 / C = 64 / C = 
 V < 64 with C > 64.  First the plan query proves the branch is reached; then every output is
 compared with the numpy statement (tests/*_cases.py) and with the host mirror, bit for bit (pred to
 minsum_cases.pred_tolerance); then the same cases run under the bounds-checked debug library."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
@@ -19,6 +14,7 @@ import torch
 from gnndecode import ops
 
 import bposd_cases as bc
+import debug_child
 import minsum_cases as mc
 import minsum_layered_cases as lc
 import osd_cases as oc
@@ -29,8 +25,6 @@ import synthetic_debug_worker as work
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEBUG_LIB = os.path.join(ROOT, 'gnn-decode_amd', 'gnndecode', 'libgnnd_debug.so')
 REFS = {'flooding': mc.reference, 'layered': lc.reference}
 
 
@@ -181,15 +175,9 @@ def test_device_equals_reference_and_host_mirror(case):
 def test_debug_library_runs_every_case_clean(tmp_path):
     """Every case above under the bounds-checked build (GNND_LIB, a fresh child process): no index
     check fires in any translation unit, and the bits are the references' and the mirrors'."""
-    assert os.path.exists(DEBUG_LIB), 'build it: make -C gnn-decode_amd debug'
     npz = str(tmp_path / 'outputs.npz')
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'synthetic_debug_worker.py'),
-                        npz], env=dict(os.environ, GNND_LIB=DEBUG_LIB), capture_output=True,
-                       text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])
-    assert res['debug'] == 1 and res['cases'] == len(work.CASES)
-    assert res['flags'] == 0, f"debug index checks fired: bits {res['flags']:#x}"
+    res = debug_child.run('synthetic_debug_worker.py', npz)
+    assert res['cases'] == len(work.CASES)
     with np.load(npz) as z:
         for case in work.CASES:
             out = []

@@ -8,10 +8,6 @@ LDS boundary on rings; stream capture; the registered ops; the bounds-checked de
 the composition with bpgd."""
 import ctypes
 import gc
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -21,15 +17,13 @@ import gnndecode as gd
 from gnndecode import _lib, ops
 
 import bpgd_cases as bc
+import debug_child
 import minsum_cases as mc
 import uf_cases as uc
 
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, 'gnn-decode_amd', 'gnndecode')
-DEBUG_LIB = os.path.join(PKG, 'libgnnd_debug.so')
 
 _GRAPHS = {}
 
@@ -308,14 +302,7 @@ def test_debug_library_runs_uf_clean():
     """toric-5 B = 67 (fp64), ring-130 (fp32) and two_comp with an unsatisfiable codeword under the
     bounds-checked build (GNND_LIB, a fresh child process): no index check fires and the bits are
     the statement's."""
-    assert os.path.exists(DEBUG_LIB), 'build it: make -C gnn-decode_amd debug'
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'uf_debug_worker.py')],
-                       env=dict(os.environ, GNND_LIB=DEBUG_LIB), capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])
-    assert res['debug'] == 1
-    assert res['flags'] == 0, f"debug index checks fired: bits {res['flags']:#x}"
+    res = debug_child.run('decoder_debug_worker.py', 'uf')
     assert res['equal'] and all(res['equal'].values()), res['equal']
 
 

@@ -7,10 +7,6 @@ inputs; the LDS boundary on rings; belief_find on toric-5; stream capture; the r
 bounds-checked debug library."""
 import ctypes
 import gc
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,6 +15,7 @@ import torch
 import gnndecode as gd
 from gnndecode import _lib, ops
 
+import debug_child
 import minsum_cases as mc
 import uf_cases as uc
 import ufw_cases as wc
@@ -26,9 +23,6 @@ import ufw_cases as wc
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, 'gnn-decode_amd', 'gnndecode')
-DEBUG_LIB = os.path.join(PKG, 'libgnnd_debug.so')
 
 _GRAPHS = {}
 
@@ -421,12 +415,5 @@ def test_debug_library_runs_ufw_clean():
     """toric-5 (fp64, llr), ring-130 (fp32, priors), two_comp with unsatisfiable codewords and
     belief_find on toric-5 under the bounds-checked build (GNND_LIB, a fresh child process): no
     index check fires and the bits are the statement's."""
-    assert os.path.exists(DEBUG_LIB), 'build it: make -C gnn-decode_amd debug'
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'ufw_debug_worker.py')],
-                       env=dict(os.environ, GNND_LIB=DEBUG_LIB), capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])
-    assert res['debug'] == 1
-    assert res['flags'] == 0, f"debug index checks fired: bits {res['flags']:#x}"
+    res = debug_child.run('decoder_debug_worker.py', 'ufw')
     assert res['equal'] and all(res['equal'].values()), res['equal']
